@@ -68,6 +68,27 @@ def scripted_guesses(vocab_words, n_eps, n_turns, batch, seed=12345):
     return g
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Writes `arrays` (name -> tensor, all with the batch as leading dim) as out_dir/<name>.npy: float32 stays float32, every other dtype is
+    widened to float64 (exact for the int32 / uint8 records).  Above DUMP_LIMIT_BYTES in all, the same seeded sample of batch rows is taken
+    from every array and its row indices are written as sample_rows.npy."""
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: a if a.dtype == np.float32 else a.astype(np.float64) for k, a in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n_keep = int(DUMP_LIMIT_BYTES // (total / n + 8))       # (+ 8 bytes per row: sample_rows itself)
+        rows = np.sort(np.random.RandomState(seed).choice(n, n_keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _cpu_rollout(vocab_words, n_envs, max_turns, budget_s):
     """The reference's per-turn structure on the host cores: re-prefill the whole history, then decode with a KV cache (HF PyTorch
     GPT2LMHeadModel as the port of the JAX model), env = the C oracle.  Returns (env steps, seconds, turns run)."""
@@ -794,7 +815,14 @@ def main():
     ap.add_argument("--ppo-train-steps", type=int, default=4, help="`ppo_iteration` leg: gradient steps per iteration (32 sequences each)")
     ap.add_argument("--ppo-max-length", type=int, default=1024, help="`ppo_iteration` leg: blocking width of the PPO data / train batches (the script's 512 + 512)")
     ap.add_argument("--train-steps", type=int, default=5, help="timed steps per arithmetic mode in the `train_step` leg of the default line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the episode records of the last timed step (the `traj` arrays a caller of replay_episode / "
+                         "run_episode receives, rank 0's envs) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array by array")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "rollout" or args.mode_rl_reduce_only):
+        ap.error("--dump-outputs: only for the headline rollout (--mode rollout, without --mode-rl-reduce-only)")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: spawn the N ranks ourselves (an external torch.distributed.run launch sets WORLD_SIZE and skips this)
         sys.exit(_spawn_ranks(sys.argv[1:], args.gpus))
@@ -905,6 +933,9 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     L.lmrl_prof_enable(0)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's records, before the legs below reuse the engines' buffers
+        dump_outputs(args.dump_outputs, {n: torch.cat([r.traj[n] for r in ros]) for n in ro.traj})
     # what a drop-in caller of `text_env_eval` pays on top of the device episode (LLM_RL/environment.py:211-267 returns HOST lists of
     # InteractionTransition): device -> host copy of the records + building the Python objects for this rank's B envs.  Outside `value`.
     th = time.perf_counter()

@@ -1,6 +1,10 @@
 """Generates tests/golden/chess_perft.json with Stockfish 15.1 built from the reference's own sources (oracle/_ref/stockfish, see oracle/Makefile):
 random playouts from the initial position and from test positions for castling, en passant, promotion and pins; for every position the legal
-move set (`go perft 1`), the FEN and the check flag (`d`).  Run here (needs /root/reference at build time); the JSON is committed."""
+move set (`go perft 1`), the FEN and the check flag (`d`).  Run here (needs /root/reference at build time); the JSON is committed.
+
+Also generates tests/golden/chess_live_playouts.json: the engine's answers along the playouts of tests/test_chess_rules.py's
+test_live_against_reference_stockfish (LIVE_SEED, a uniform choice over the SORTED legal moves each ply), which that test reads wherever the
+engine binary is not built."""
 import json
 import os
 import random
@@ -48,5 +52,30 @@ def main():
     print(out, sum(len(g["steps"]) for g in games), "positions", os.path.getsize(out), "bytes")
 
 
+LIVE_SEED, LIVE_GAMES, LIVE_PLIES = 123, 12, 120
+
+
+def live_playouts():
+    eng = S.Engine()
+    rng = random.Random(LIVE_SEED)
+    games = []
+    for g in range(LIVE_GAMES):
+        moves, steps = [], []
+        for ply in range(LIVE_PLIES):
+            legal = eng.perft1(START, moves)
+            f, chk = eng.describe(START, moves)
+            steps.append(dict(fen=f, legal=" ".join(legal), check=chk))
+            if not legal:
+                break
+            moves.append(rng.choice(legal))
+        games.append(dict(moves=moves, steps=steps))
+    eng.close()
+    out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "chess_live_playouts.json")
+    json.dump(dict(engine="Stockfish 15.1 (reference stockfish/src, classical evaluation)", start=START, seed=LIVE_SEED, games=games),
+              open(out, "w"), separators=(",", ":"))
+    print(out, sum(len(g["steps"]) for g in games), "positions", os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
     main()
+    live_playouts()

@@ -1,7 +1,8 @@
 """CPU tier: the chess rules of csrc/chess_rules.h (host entry points of liblmrl_amd.so — the same code the device kernels run) against
 (a) the committed fixtures produced by Stockfish 15.1 built from the reference's own sources (tests/golden/chess_perft.json: legal move sets
     and positions along random playouts from the initial position and from castling / en-passant / promotion / pin test positions),
-(b) the live engine when oracle/_ref/stockfish is present (fresh random playouts),
+(b) the live engine when oracle/_ref/stockfish is present, otherwise its answers recorded along the same random playouts
+    (tests/golden/chess_live_playouts.json),
 (c) properties of the SAN layer, which no oracle in this image can pin (python-chess is absent): san(move) -> parse_san round trip over every
     legal move of every visited position, hand-checked SAN strings, the regex corner cases of python-chess parse_san, and
 (d) the termination rules (checkmate, stalemate, insufficient material, 75-move rule, fivefold repetition).
@@ -10,8 +11,6 @@ import ctypes
 import json
 import os
 import random
-
-import pytest
 
 import lmrl_gym_amd  # noqa: F401
 from lmrl_gym_amd import _lib
@@ -87,17 +86,42 @@ def test_fixtures_from_reference_stockfish():
     assert n_pos >= 1500
 
 
+class RecordedEngine:
+    """The engine's answers along the playouts of test_live_against_reference_stockfish, as recorded by tests/golden/make_fixtures_chess.py
+    (tests/golden/chess_live_playouts.json): stands in for the live engine wherever oracle/_ref/stockfish is not built."""
+
+    def __init__(self):
+        fx = json.load(open(os.path.join(HERE, "golden", "chess_live_playouts.json")))
+        self.start, self.pos = fx["start"], {}
+        for game in fx["games"]:
+            for ply, step in enumerate(game["steps"]):
+                self.pos[" ".join(game["moves"][:ply])] = step
+
+    def _step(self, fen, moves):
+        key = " ".join(moves)
+        assert fen == self.start and key in self.pos, ("position not in the recorded playouts", fen, key)
+        return self.pos[key]
+
+    def perft1(self, fen, moves=()):
+        return self._step(fen, moves)["legal"].split()
+
+    def describe(self, fen, moves=()):
+        st = self._step(fen, moves)
+        return st["fen"], st["check"]
+
+    def close(self):
+        pass
+
+
 def test_live_against_reference_stockfish():
     from oracle import stockfish_uci as S
-    if not S.available():
-        pytest.skip("oracle/_ref/stockfish not built (needs /root/reference at build time)")
-    eng = S.Engine()
-    rng = random.Random(123)
+    eng = S.Engine() if S.available() else RecordedEngine()
+    rng = random.Random(123)            # (moves drawn from the sorted legal list: the recorded playouts follow the same draws)
     for g in range(12):
         b, moves = Board(START), []
         for ply in range(120):
-            legal = b.legal()
-            assert sorted(u for u, _ in legal) == eng.perft1(START, moves)
+            legal = sorted(b.legal())
+            assert [u for u, _ in legal] == eng.perft1(START, moves)
             f, chk = eng.describe(START, moves)
             _same_position(b.fen(), f, [u for u, _ in legal])
             assert bool(b.status() & 1) == chk

@@ -1,6 +1,7 @@
 """GPU tier: the batched chess env (lmrl_gym_amd.envs.chess, csrc/chess.hip) — the device half-step kernels against the host faces of the same
 rules (pinned to the reference's Stockfish in tests/test_chess_rules.py), the reward / done / observation conventions of
-llm_rl_scripts/chess/env/env.py:91-238, the text protocol classes, and games against the engine built from the reference sources."""
+llm_rl_scripts/chess/env/env.py:91-238, the text protocol classes, and games against the engine built from the reference sources (where it is not built: against
+tests/uci_standin.cpp, the same UCI dialogue over this package's rules)."""
 import os
 import random
 import sys
@@ -16,8 +17,20 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def _engine_path():
-    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "stockfish")
-    return p if os.path.exists(p) else None
+    """The engine built from the reference sources when present, otherwise tests/uci_standin.cpp (the package's own rules behind the same
+    UCI dialogue, legal moves from a fixed-seed stream) built for the host into tests/_build/."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = os.path.join(root, "oracle", "_ref", "stockfish")
+    if os.path.exists(p):
+        return p
+    src = os.path.join(root, "tests", "uci_standin.cpp")
+    exe = os.path.join(root, "tests", "_build", "uci_standin")
+    deps = [src, os.path.join(root, "lmrl-gym_amd", "csrc", "chess_rules.h")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        import subprocess
+        os.makedirs(os.path.dirname(exe), exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, src])
+    return exe
 
 
 class ScriptedChessPolicy:
@@ -214,8 +227,6 @@ def test_mate_stalemate_null_move_and_text_classes():
 def test_games_against_the_reference_engine():
     from lmrl_gym_amd.envs import chess as C
     path = _engine_path()
-    if path is None:
-        pytest.skip("oracle/_ref/stockfish not present")
     from test_chess_rules import Board
     B = 6
     env = C.VectorChessEnv(max_moves=12, engine_path=path, engine_options={"Use NNUE": "false"}, movetime_ms=20)

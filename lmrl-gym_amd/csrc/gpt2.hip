@@ -1233,7 +1233,7 @@ static int gpt2_forward_impl(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, con
     // stores over 128 envs' cache pages), a net loss of 1.2 us per layer — so it is off by default and kept as a per-call variant.
     const bool kv_from_gemm = fused && c == 1 && (flags & LMRL_FWD_KV_FROM_GEMM) && !(flags & LMRL_FWD_ATTN_VALU);
     // LMRL_FWD_SKINNY (single-token decode of <= 16 sequences, LN-folded path): the four Dense products of a layer on skinny_gemm.h (one MFMA row block,
-    // K split over the 16 waves of a workgroup, every operand load issued up front) instead of the 64 x 64-tile latency chains
+    // K split over the 8 waves (kSkKS) of a workgroup, every operand load issued up front) instead of the 64 x 64-tile latency chains
     // (the skinny residual producers write no LayerNorm slots, the skinny consumers read the fp32 rows instead: all of a layer's products switch together;
     //  GPT-2-small / medium / large all qualify: K = d_model / d_ff of all three; other widths keep the whole session on the tile kernels)
     bool skinny = fused && c == 1 && (flags & LMRL_FWD_SKINNY) && M <= 16 && !kv_from_gemm;

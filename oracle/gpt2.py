@@ -27,8 +27,11 @@ def layer_norm(x, g, b, eps):
 
 def forward(sd: Dict[str, torch.Tensor], input_ids: torch.Tensor, n_head: int, eps: float = 1e-5,
             attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
-            dtype=torch.float64, return_hidden: bool = False):
-    """input_ids [B, T] -> logits [B, T, V] (and final-LN hidden states [B, T, d])."""
+            dtype=torch.float64, return_hidden: bool = False, return_kv: bool = False):
+    """input_ids [B, T] -> logits [B, T, V] (and final-LN hidden states [B, T, d]).
+    return_kv: also return every layer's K and V as lists of [B, T, d] tensors, heads interleaved as in `c_attn`'s
+    columns (the engine's cache layout: K of layer l at `kv.view(2 * n_layer, B, tmax, d)[2 l]`, V at [2 l + 1]).
+    Returns logits, then hid if return_hidden, then (ks, vs) if return_kv."""
     sd = {k: v.to(dtype) for k, v in sd.items()}
     B, T = input_ids.shape
     if position_ids is None:
@@ -38,10 +41,13 @@ def forward(sd: Dict[str, torch.Tensor], input_ids: torch.Tensor, n_head: int, e
     hd = d // n_head
     causal = torch.tril(torch.ones(T, T, dtype=torch.bool))
     n_layer = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("h."))
+    ks, vs = [], []
     for l in range(n_layer):
         p = f"h.{l}."
         h = layer_norm(x, sd[p + "ln_1.weight"], sd[p + "ln_1.bias"], eps)
         qkv = h @ sd[p + "attn.c_attn.weight"] + sd[p + "attn.c_attn.bias"]
+        if return_kv:
+            ks.append(qkv[..., d:2 * d]); vs.append(qkv[..., 2 * d:])
         q, k, v = (t.reshape(B, T, n_head, hd).transpose(1, 2) for t in qkv.split(d, dim=-1))
         att = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
         mask = causal[None, None]
@@ -54,7 +60,8 @@ def forward(sd: Dict[str, torch.Tensor], input_ids: torch.Tensor, n_head: int, e
         x = x + gelu_new(h @ sd[p + "mlp.c_fc.weight"] + sd[p + "mlp.c_fc.bias"]) @ sd[p + "mlp.c_proj.weight"] + sd[p + "mlp.c_proj.bias"]
     hid = layer_norm(x, sd["ln_f.weight"], sd["ln_f.bias"], eps)
     logits = hid @ sd["wte.weight"].t()
-    return (logits, hid) if return_hidden else logits
+    out = (logits,) + ((hid,) if return_hidden else ()) + (((ks, vs),) if return_kv else ())
+    return out if len(out) > 1 else logits
 
 
 def round_weights_to_bf16(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -683,24 +683,36 @@ def test_sampler_steer_and_ilql_perturbation(dev):
 def test_ragged_prefill_is_bit_identical(dev):
     """Chunk forwards on the compacted rows (sum of cnt) vs on all B*C slots: same last hidden states, same KV cache, same
     cache lengths, bit for bit, for ragged counts including empty envs; decode steps afterwards agree too."""
+    _ragged_prefill_is_bit_identical(dev, 48)
+
+
+def test_ragged_prefill_is_bit_identical_long_context(dev):
+    """test_ragged_prefill_is_bit_identical after a long prefill (tmax = 1024, cache lengths past 512): the variants' decode attention
+    over every position batch of a long context."""
+    _ragged_prefill_is_bit_identical(dev, 1024)
+
+
+def _ragged_prefill_is_bit_identical(dev, tmax):
     from lmrl_gym_amd.gpt2 import GPT2Config, GPT2Engine, init_hf_style_state_dict
-    cfg = GPT2Config(2, 12, 768, 3072, 1000, 64)
+    cfg = GPT2Config(2, 12, 768, 3072, 1000, max(64, tmax))
     eng = GPT2Engine(cfg, init_hf_style_state_dict(cfg, seed=2), dev)
     B = 37
     g = torch.Generator().manual_seed(1)
     plan = [(8, torch.randint(0, 9, (B,), generator=g)), (16, torch.randint(0, 17, (B,), generator=g)), (1, torch.randint(0, 2, (B,), generator=g)),
             (1, torch.ones(B, dtype=torch.int64)), (8, torch.randint(3, 9, (B,), generator=g))]
     plan[0][1][0] = 0; plan[0][1][B - 1] = 8
+    if tmax > 48:
+        plan[2:2] = [(16, torch.randint(9, 17, (B,), generator=g)) for _ in range(44)] + [(8, torch.randint(0, 9, (B,), generator=g))]
     outs = []
     from lmrl_gym_amd.gpt2 import FWD_ATTN_ITEMS2, FWD_ATTN_ITEMS3, FWD_FULL_LAST_LAYER, FWD_KV_FROM_GEMM, FWD_RAGGED_ALWAYS, FWD_RAGGED_NEVER
     # the sessions are INTERLEAVED forward by forward: the variant is a property of the call, not of the process.  FWD_KV_FROM_GEMM: the
     # decode qkv GEMM's epilogue appends the new K / V rows instead of the attention kernel — same cache bytes, same outputs
-    sess = [eng.session(B, 48, flags=FWD_RAGGED_ALWAYS), eng.session(B, 48, flags=FWD_RAGGED_NEVER),
-            eng.session(B, 48, flags=FWD_RAGGED_ALWAYS | FWD_KV_FROM_GEMM), eng.session(B, 48, flags=FWD_RAGGED_NEVER | FWD_KV_FROM_GEMM),
+    sess = [eng.session(B, tmax, flags=FWD_RAGGED_ALWAYS), eng.session(B, tmax, flags=FWD_RAGGED_NEVER),
+            eng.session(B, tmax, flags=FWD_RAGGED_ALWAYS | FWD_KV_FROM_GEMM), eng.session(B, tmax, flags=FWD_RAGGED_NEVER | FWD_KV_FROM_GEMM),
             # FWD_FULL_LAST_LAYER: the last layer's projection + MLP on every chunk row instead of on each env's last new token only (the default)
-            eng.session(B, 48, flags=FWD_RAGGED_ALWAYS | FWD_FULL_LAST_LAYER), eng.session(B, 48, flags=FWD_RAGGED_NEVER | FWD_FULL_LAST_LAYER),
+            eng.session(B, tmax, flags=FWD_RAGGED_ALWAYS | FWD_FULL_LAST_LAYER), eng.session(B, tmax, flags=FWD_RAGGED_NEVER | FWD_FULL_LAST_LAYER),
             # FWD_ATTN_ITEMS2 / 3 (round 6, A/B): decode attention on a grid of half / a third as many waves, 2 / 3 (env, head) items per wave
-            eng.session(B, 48, flags=FWD_ATTN_ITEMS2), eng.session(B, 48, flags=FWD_RAGGED_ALWAYS | FWD_ATTN_ITEMS3)]
+            eng.session(B, tmax, flags=FWD_ATTN_ITEMS2), eng.session(B, tmax, flags=FWD_RAGGED_ALWAYS | FWD_ATTN_ITEMS3)]
     hs = [[] for _ in sess]
     for C, cnt in plan:
         toks = torch.randint(0, cfg.vocab, (B * C,), generator=torch.Generator().manual_seed(C)).to(torch.int32).to(dev)
@@ -716,7 +728,7 @@ def test_ragged_prefill_is_bit_identical(dev):
 @pytest.mark.parametrize("B,model", [(8, "small"), (16, "small"), (3, "small"), (8, "medium")])
 def test_skinny_decode_products_equal_the_tile_kernels(dev, B, model):
     """LMRL_FWD_SKINNY (round 6; configs[0]'s 8-env batch): decode forwards of <= 16 sequences run their four Dense products per layer on
-    csrc/skinny_gemm.h (one MFMA row block, K split over the 16 waves of a workgroup) instead of the 64 x 64-tile kernels.  Same formulas, K summed
+    csrc/skinny_gemm.h (one MFMA row block, K split over the 8 waves of a workgroup) instead of the 64 x 64-tile kernels.  Same formulas, K summed
     in 8 slices: hidden states and K/V rows agree with the default session to bf16 rounding over a prefill + 12 decode steps (ragged counts,
     finished rows, both row-compaction modes), at GPT-2-small and GPT-2-medium widths."""
     from lmrl_gym_amd.gpt2 import FWD_RAGGED_ALWAYS, FWD_SKINNY, GPT2Config, GPT2Engine, init_hf_style_state_dict
@@ -756,10 +768,20 @@ def test_indexed_prefix_attention_equals_copied_prefix(dev, B, group):
     `gather_prefix_from` (rows copied per env): same hidden states after every decode step and the same generated-token rows in the
     env caches, bit for bit — ragged prompt lengths, envs without a prompt (idx < 0), finished envs (cnt = 0), both launch orders
     (B = 256 with 12 heads: a grid the XCD-grouped order applies to)."""
+    _indexed_prefix_attention_equals_copied_prefix(dev, B, group, 32)
+
+
+def test_indexed_prefix_attention_equals_copied_prefix_long_context(dev):
+    """test_indexed_prefix_attention_equals_copied_prefix with prompts of up to 1008 tokens: prompt rows past 512 read from the prefix
+    session, generated rows up to position 1015."""
+    _indexed_prefix_attention_equals_copied_prefix(dev, 37, True, 1008)
+
+
+def _indexed_prefix_attention_equals_copied_prefix(dev, B, group, cap):
     from lmrl_gym_amd.gpt2 import FWD_KV_FROM_GEMM, GPT2Config, GPT2Engine, init_hf_style_state_dict
-    cfg = GPT2Config(2, 12, 768, 3072, 1000, 64)
+    cfg = GPT2Config(2, 12, 768, 3072, 1000, max(64, cap + 8))
     eng = GPT2Engine(cfg, init_hf_style_state_dict(cfg, seed=4), dev)
-    R, cap, tmax = 9, 32, 40
+    R, tmax = 9, cap + 8
     g = torch.Generator().manual_seed(7)
     src = eng.session(R, cap)
     src.reset()

@@ -31,6 +31,59 @@ def test_oracle_gpt2_matches_hf_pytorch():
     torch.testing.assert_close(got[m], ref[m], rtol=1e-4, atol=1e-4)
 
 
+def _hf_layer_kv(pkv, l):
+    """(K, V) of layer l from HF `past_key_values` [B, H, T, hd], across the cache classes of transformers releases."""
+    if hasattr(pkv, "layers"):
+        return pkv.layers[l].keys, pkv.layers[l].values
+    if hasattr(pkv, "key_cache"):
+        return pkv.key_cache[l], pkv.value_cache[l]
+    return pkv[l][0], pkv[l][1]
+
+
+@pytest.mark.parametrize("masked", [False, True])
+def test_oracle_gpt2_kv_matches_hf_past_key_values(masked):
+    """`forward(..., return_kv=True)`: every layer's K and V [B, T, d] (heads interleaved as in c_attn's columns, the engine's cache
+    layout) equal HF's `past_key_values` (use_cache=True), and the logits / hidden states are the same as without the flag."""
+    transformers = pytest.importorskip("transformers")
+    from oracle import gpt2 as O
+    n_layer, n_head, d = 3, 4, 64
+    cfg = transformers.GPT2Config(vocab_size=211, n_positions=48, n_embd=d, n_layer=n_layer, n_head=n_head,
+                                  resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0)
+    torch.manual_seed(1)
+    model = transformers.GPT2LMHeadModel(cfg).eval()
+    with torch.no_grad():
+        for n, p in model.named_parameters():
+            if p.dim() == 1:
+                p.add_(torch.randn_like(p) * 0.1)
+    sd = {k[len("transformer."):]: v for k, v in model.state_dict().items() if k.startswith("transformer.") and not k.endswith(".attn.bias") and "masked_bias" not in k}
+    B, T = 3, 23
+    ids = torch.randint(0, 211, (B, T))
+    kw, hw = {}, {}
+    if masked:
+        am = torch.ones(B, T, dtype=torch.long); am[1, 15:] = 0; am[2, 6:] = 0
+        pos = (am.cumsum(-1) - 1).clamp(min=0)
+        kw = dict(attention_mask=am, position_ids=pos)
+        hw = dict(attention_mask=am, position_ids=pos)
+    with torch.no_grad():
+        out = model(ids, use_cache=True, **hw)
+    logits, hid, (ks, vs) = O.forward(sd, ids, n_head=n_head, dtype=torch.float32, return_hidden=True, return_kv=True, **kw)
+    logits0, hid0 = O.forward(sd, ids, n_head=n_head, dtype=torch.float32, return_hidden=True, **kw)
+    assert torch.equal(logits, logits0) and torch.equal(hid, hid0)
+    assert len(ks) == len(vs) == n_layer
+    for l in range(n_layer):
+        hk, hv = _hf_layer_kv(out.past_key_values, l)
+        assert ks[l].shape == vs[l].shape == (B, T, d)
+        # [B, H, T, hd] -> [B, T, H * hd]: head h at columns [h * hd, (h + 1) * hd)
+        torch.testing.assert_close(ks[l], hk.transpose(1, 2).reshape(B, T, d), rtol=1e-5, atol=1e-5)
+        torch.testing.assert_close(vs[l], hv.transpose(1, 2).reshape(B, T, d), rtol=1e-5, atol=1e-5)
+    # float64: the same rows as float32 to float32 rounding (the GPU tier compares against the float64 form)
+    _, (k64, v64) = O.forward(sd, ids, n_head=n_head, dtype=torch.float64, return_kv=True, **kw)
+    assert k64[0].dtype == torch.float64
+    for l in range(n_layer):
+        torch.testing.assert_close(k64[l].float(), ks[l], rtol=1e-5, atol=1e-5)
+        torch.testing.assert_close(v64[l].float(), vs[l], rtol=1e-5, atol=1e-5)
+
+
 def test_philox_known_answer():
     # Random123 known-answer test vector for philox4x32-10: counter = key = 0 and all-ones
     import numpy as np

@@ -731,11 +731,18 @@ int lmrl_prof_read(int tag, double *total_ms, double *total_work, long long *lau
  * LLM_RL/algorithms/ilql/gpt2/interface.py:88-367) in float32, the reference's default parameter/activation dtype.
  * ------------------------------------------------------------------------------------------ */
 /* C[b] = alpha*op(A[b]).op(B[b]) + beta*C[b] (+bias[n]); row-major; op(A) MxK (trans_a: stored KxM), op(B) KxN
- * (trans_b: stored NxK); batch index = outer*nb_inner + inner with separate element strides. Exact fp32 (MFMA f32). */
+ * (trans_b: stored NxK); batch index = outer*nb_inner + inner with separate element strides. Exact fp32 (MFMA f32).
+ * Unbatched products with few output tiles and a long K split K across workgroups: the partial products go to the caller's
+ * workspace ws_d and a fixed-order reduce adds them (deterministic).  lmrl_sgemm_ws_bytes(m, n, k, nb_outer * nb_inner) is
+ * its size, 0 when the product does not split; a splitting call with a NULL or smaller workspace fails before it launches
+ * anything.  A captured graph keeps ws_d, and calls in flight on different streams need workspaces of their own. */
+size_t lmrl_sgemm_ws_bytes(int m, int n, int k, int batch);
 int lmrl_sgemm(int trans_a, int trans_b, int m, int n, int k, float alpha, const float *a_d, int lda, long sa_outer,
                long sa_inner, const float *b_d, int ldb, long sb_outer, long sb_inner, float beta, float *c_d, int ldc,
-               long sc_outer, long sc_inner, int nb_outer, int nb_inner, const float *bias_d, void *stream);
-/* A/B hook: 0 = auto (128x128 tiles when m, n >= 128), 1 = always the 64x64-tile kernel */
+               long sc_outer, long sc_inner, int nb_outer, int nb_inner, const float *bias_d, void *ws_d, size_t ws_bytes,
+               void *stream);
+/* A/B hook: 0 = auto (128x128 tiles when m, n >= 128, split K as above), 1 = always the 64x64-tile kernel, never split
+ * (lmrl_sgemm_ws_bytes follows the setting) */
 void lmrl_sgemm_set_variant(int v);
 /* TOOLS / TESTS ONLY: bit 0 = LayerNorm forward, bit 1 = fused LayerNorm backward on the strided 4-byte-access kernels (A/B of the 16-byte-access
  * register-row kernels) */

@@ -128,7 +128,9 @@ _SIGS = {
     "lmrl_prof_tag_name": (c_char_p, [c_int]),
     "lmrl_prof_read": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
     "lmrl_sgemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, ctypes.c_long, ctypes.c_long, c_void_p, c_int,
-                           ctypes.c_long, ctypes.c_long, c_float, c_void_p, c_int, ctypes.c_long, ctypes.c_long, c_int, c_int, c_void_p, c_void_p]),
+                           ctypes.c_long, ctypes.c_long, c_float, c_void_p, c_int, ctypes.c_long, ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                           c_void_p]),
+    "lmrl_sgemm_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "lmrl_embed_fwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
     "lmrl_cast_bf16": (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_void_p, ctypes.c_long, c_int, c_int, c_void_p]),
     "lmrl_cast_bf16_segments": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -1,4 +1,4 @@
-// sgemm_f32.hip — exact-fp32 batched GEMM on the CDNA4 matrix cores (v_mfma_f32_32x32x2_f32) for the TRAIN path.
+// sgemm_f32.hip — exact-fp32 batched GEMM on the CDNA4 matrix cores (v_mfma_f32_32x32x2_f32) for the train path and the fp32 rollout engine.
 //
 // The reference trains in float32 (`jnp.float32` params / activations in LLM_RL/algorithms/{ppo,ilql}/gpt2/interface.py
 // and the heads), and BASELINE.json asks for ILQL train-step outputs within 1e-4 relative: the forward/backward GEMMs of
@@ -287,84 +287,84 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
 
 using namespace lmrl;
 
-// process-wide split-K workspace (train path only; grown on demand, never inside a graph capture)
-static float *g_splitk_ws = nullptr;
-static size_t g_splitk_ws_floats = 0;
-
-extern "C" void lmrl_sgemm_set_variant(int v);
 static int g_sgemm_variant = 0;   // 0: auto, 1: always the 64 x 64 tile kernel (A/B hook)
 void lmrl_sgemm_set_variant(int v) { g_sgemm_variant = v; }
 
+// How one lmrl_sgemm call runs: `tile` is the output tile edge (128 or 64); S > 1 splits K into S slices of kc (the last one shorter) whose
+// partial products go to the caller's workspace (S * m * n floats) before a fixed-order reduce.  lmrl_sgemm and lmrl_sgemm_ws_bytes both take
+// it from here, so the split decision is made in one place.
+struct SgemmPlan { int tile, S, kc; };
 
-extern "C" int lmrl_sgemm(int trans_a, int trans_b, int m, int n, int k, float alpha, const float *a_d, int lda, long sa_outer,
-                          long sa_inner, const float *b_d, int ldb, long sb_outer, long sb_inner, float beta, float *c_d, int ldc,
-                          long sc_outer, long sc_inner, int nb_outer, int nb_inner, const float *bias_d, void *stream) {
-    LMRL_REQUIRE(a_d && b_d && c_d && m > 0 && n > 0 && k > 0 && nb_outer > 0 && nb_inner > 0, "lmrl_sgemm: bad argument");
-    SgemmArgs g{a_d, b_d, c_d, bias_d, m, n, k, lda, ldb, ldc, sa_outer, sa_inner, sb_outer, sb_inner, sc_outer, sc_inner,
-                nb_inner, alpha, beta};
-    hipStream_t s = as_stream(stream);
+static SgemmPlan sgemm_plan(int m, int n, int k, int batch) {
+    SgemmPlan p{g_sgemm_variant != 1 && m >= 128 && n >= 128 ? 128 : 64, 1, k};   // large GEMMs: 128 x 128 tiles (2 x 2 MFMA tiles per wave)
     // Weight-gradient shapes (dW = X^T dY: small M x N, K = all tokens of the batch) have fewer 128 x 128 tiles than CUs:
     // split K across workgroups into a workspace and add the partials in a fixed order (no atomics -> deterministic).
     // The fp32 ROLLOUT's decode products (M = one row per env, ~1024; gpt2_f32_engine.py) have the same problem at a short K: the output
     // projections (N = d_model) are 48 tiles of 128 x 128 on 256 CUs — K = 768 / 3072 split 3 / 5 ways puts a workgroup on (almost) every CU
     // (41 -> ~17 us and 164 -> ~40 us by the cost model below); slices down to 128 long are allowed there.
-    const long tiles0 = (long)ceil_div(n, SG2_BN) * ceil_div(m, SG2_BM);
-    const bool short_k_few_tiles = m <= 2048 && k >= 512 && tiles0 <= 160;
-    if (g_sgemm_variant == 0 && m >= 128 && n >= 128 && nb_outer * nb_inner == 1 && (k >= 4096 || short_k_few_tiles)) {
-        const long tiles = tiles0;
-        const int min_slice = k >= 4096 ? 1024 : 128;
-        // S slices: tiles * S workgroups run in rounds of the 256 CUs and a round costs one slice (K / S), so time ~ ceil(tiles S / 256) / S — S = 4
-        // on 144 tiles is 2.25 rounds = 3 (0.75 of a full-K tile time, the measured 85 vs 113 TFLOP/s), S = 7 is 3.94 = 4 (0.57) — plus the
-        // partials' round trip through HBM (2 S m n floats at ~5 TB/s against ~0.5 TFLOP/s per CU).  Slices of unequal length (the last one shorter).
-        // (also above 256 tiles: 384 tiles — the vocabulary heads' dX, K = 50 257 — are 1.5 rounds = 2 unsplit, 3 rounds of half the K when split in two)
-        int S = 1, kc = k;
-        if (tiles < 1024) {
-            double best = 1e300;
-            const double t_tile = 2.0 * SG2_BM * SG2_BN * (double)k / 0.5e12, t_part = 8.0 * (double)m * n / 5e12;
-            for (int c = 1; c <= 16; c++) {
-                const int per = ceil_div(ceil_div(k, SG2_BK), c) * SG2_BK;      // slice length, a multiple of the K-step
-                const int slices = ceil_div(k, per);
-                if (c > 1 && (per < min_slice || slices < 2)) continue;
-                const double cost = (double)ceil_div((int)(tiles * slices), 256) * t_tile * per / k + (slices > 1 ? slices * t_part : 0.0);
-                if (cost < best - 1e-12) { best = cost; S = slices; kc = per; }
-            }
-        }
-        if (S > 1) {
-            const size_t need = (size_t)S * m * n;
-            if (need > g_splitk_ws_floats) {
-                if (g_splitk_ws) { LMRL_CHECK_HIP(hipStreamSynchronize(s)); LMRL_CHECK_HIP(hipFree(g_splitk_ws)); g_splitk_ws = nullptr; g_splitk_ws_floats = 0; }
-                LMRL_CHECK_HIP(hipMalloc(&g_splitk_ws, need * sizeof(float)));
-                g_splitk_ws_floats = need;
-            }
-            SgemmArgs gs{a_d, b_d, g_splitk_ws, nullptr, m, n, kc, lda, ldb, n,
-                         trans_a ? (long)kc * lda : (long)kc, 0, trans_b ? (long)kc : (long)kc * ldb, 0, (long)m * n, 0, 1, 1.f, 0.f, k};
-            dim3 grid2(ceil_div(n, SG2_BN), ceil_div(m, SG2_BM), S);
-            if (!trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<false, false>), grid2, dim3(256), 0, s, gs);
-            else if (!trans_a && trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<false, true>), grid2, dim3(256), 0, s, gs);
-            else if (trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<true, false>), grid2, dim3(256), 0, s, gs);
-            else hipLaunchKernelGGL((sgemm_f32_128_kernel<true, true>), grid2, dim3(256), 0, s, gs);
-            LMRL_CHECK_LAUNCH();
-            const size_t mn = (size_t)m * n;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((mn + 1023) / 1024 < 2048 ? (mn + 1023) / 1024 : 2048)), dim3(256), 0, s,
-                               g_splitk_ws, S, m, n, c_d, ldc, alpha, beta, bias_d);
-            LMRL_CHECK_LAUNCH();
-            return LMRL_OK;
-        }
+    const long tiles = (long)ceil_div(n, SG2_BN) * ceil_div(m, SG2_BM);
+    const bool short_k_few_tiles = m <= 2048 && k >= 512 && tiles <= 160;
+    if (g_sgemm_variant != 0 || p.tile != 128 || batch != 1 || !(k >= 4096 || short_k_few_tiles) || tiles >= 1024) return p;
+    const int min_slice = k >= 4096 ? 1024 : 128;
+    // S slices: tiles * S workgroups run in rounds of the 256 CUs and a round costs one slice (K / S), so time ~ ceil(tiles S / 256) / S — S = 4
+    // on 144 tiles is 2.25 rounds = 3 (0.75 of a full-K tile time, the measured 85 vs 113 TFLOP/s), S = 7 is 3.94 = 4 (0.57) — plus the
+    // partials' round trip through HBM (2 S m n floats at ~5 TB/s against ~0.5 TFLOP/s per CU).  Slices of unequal length (the last one shorter).
+    // (also above 256 tiles: 384 tiles — the vocabulary heads' dX, K = 50 257 — are 1.5 rounds = 2 unsplit, 3 rounds of half the K when split in two)
+    double best = 1e300;
+    const double t_tile = 2.0 * SG2_BM * SG2_BN * (double)k / 0.5e12, t_part = 8.0 * (double)m * n / 5e12;
+    for (int c = 1; c <= 16; c++) {
+        const int per = ceil_div(ceil_div(k, SG2_BK), c) * SG2_BK;      // slice length, a multiple of the K-step
+        const int slices = ceil_div(k, per);
+        if (c > 1 && (per < min_slice || slices < 2)) continue;
+        const double cost = (double)ceil_div((int)(tiles * slices), 256) * t_tile * per / k + (slices > 1 ? slices * t_part : 0.0);
+        if (cost < best - 1e-12) { best = cost; p.S = slices; p.kc = per; }
     }
-    if (g_sgemm_variant != 1 && m >= 128 && n >= 128) {   // large GEMMs: 128 x 128 tiles (2 x 2 MFMA tiles per wave)
-        dim3 grid2(ceil_div(n, SG2_BN), ceil_div(m, SG2_BM), nb_outer * nb_inner);
-        if (!trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<false, false>), grid2, dim3(256), 0, s, g);
-        else if (!trans_a && trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<false, true>), grid2, dim3(256), 0, s, g);
-        else if (trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<true, false>), grid2, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((sgemm_f32_128_kernel<true, true>), grid2, dim3(256), 0, s, g);
-        LMRL_CHECK_LAUNCH();
-        return LMRL_OK;
+    return p;
+}
+
+size_t lmrl_sgemm_ws_bytes(int m, int n, int k, int batch) {
+    const SgemmPlan p = sgemm_plan(m, n, k, batch);
+    return p.S > 1 ? (size_t)p.S * m * n * sizeof(float) : 0;
+}
+
+int lmrl_sgemm(int trans_a, int trans_b, int m, int n, int k, float alpha, const float *a_d, int lda, long sa_outer, long sa_inner,
+               const float *b_d, int ldb, long sb_outer, long sb_inner, float beta, float *c_d, int ldc, long sc_outer, long sc_inner,
+               int nb_outer, int nb_inner, const float *bias_d, void *ws_d, size_t ws_bytes, void *stream) {
+    LMRL_REQUIRE(a_d && b_d && c_d && m > 0 && n > 0 && k > 0 && nb_outer > 0 && nb_inner > 0, "lmrl_sgemm: bad argument");
+    const SgemmPlan p = sgemm_plan(m, n, k, nb_outer * nb_inner);
+    SgemmArgs g{a_d, b_d, c_d, bias_d, m, n, k, lda, ldb, ldc, sa_outer, sa_inner, sb_outer, sb_inner, sc_outer, sc_inner,
+                nb_inner, alpha, beta};
+    dim3 grid(ceil_div(n, p.tile), ceil_div(m, p.tile), nb_outer * nb_inner);
+    if (p.S > 1) {   // slice z of K into partial product z of the workspace; the reduce below applies alpha, beta and the bias
+        const size_t need = (size_t)p.S * m * n * sizeof(float);
+        if (!ws_d || ws_bytes < need) {
+            set_error("lmrl_sgemm: %d x %d x %d splits K %d ways and needs %zu workspace bytes (lmrl_sgemm_ws_bytes), got %zu", m, n, k, p.S, need,
+                      ws_d ? ws_bytes : (size_t)0);
+            return LMRL_ERR_ARG;
+        }
+        const int kc = p.kc;
+        g = SgemmArgs{a_d, b_d, static_cast<float *>(ws_d), nullptr, m, n, kc, lda, ldb, n,
+                      trans_a ? (long)kc * lda : (long)kc, 0, trans_b ? (long)kc : (long)kc * ldb, 0, (long)m * n, 0, 1, 1.f, 0.f, k};
+        grid.z = p.S;
     }
-    dim3 grid(ceil_div(n, SG_BN), ceil_div(m, SG_BM), nb_outer * nb_inner);
-    if (!trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_kernel<false, false>), grid, dim3(256), 0, s, g);
-    else if (!trans_a && trans_b) hipLaunchKernelGGL((sgemm_f32_kernel<false, true>), grid, dim3(256), 0, s, g);
-    else if (trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_kernel<true, false>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((sgemm_f32_kernel<true, true>), grid, dim3(256), 0, s, g);
+    hipStream_t s = as_stream(stream);
+    if (p.tile == 128) {
+        if (!trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<false, false>), grid, dim3(256), 0, s, g);
+        else if (!trans_a && trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<false, true>), grid, dim3(256), 0, s, g);
+        else if (trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_128_kernel<true, false>), grid, dim3(256), 0, s, g);
+        else hipLaunchKernelGGL((sgemm_f32_128_kernel<true, true>), grid, dim3(256), 0, s, g);
+    } else {
+        if (!trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_kernel<false, false>), grid, dim3(256), 0, s, g);
+        else if (!trans_a && trans_b) hipLaunchKernelGGL((sgemm_f32_kernel<false, true>), grid, dim3(256), 0, s, g);
+        else if (trans_a && !trans_b) hipLaunchKernelGGL((sgemm_f32_kernel<true, false>), grid, dim3(256), 0, s, g);
+        else hipLaunchKernelGGL((sgemm_f32_kernel<true, true>), grid, dim3(256), 0, s, g);
+    }
     LMRL_CHECK_LAUNCH();
+    if (p.S > 1) {
+        const size_t mn = (size_t)m * n;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((mn + 1023) / 1024 < 2048 ? (mn + 1023) / 1024 : 2048)), dim3(256), 0, s,
+                           static_cast<const float *>(ws_d), p.S, m, n, c_d, ldc, alpha, beta, bias_d);
+        LMRL_CHECK_LAUNCH();
+    }
     return LMRL_OK;
 }

@@ -60,20 +60,21 @@ class GPT2EngineF32:
         """Bytes of split-K partial-sum workspace ONE caller needs for this engine's products on `rows` rows (0: no product takes the split-K
         path).  The workspace belongs to the CALLER (a KV session sizes it once, before any graph capture): sessions on different HIP streams
         (`text_env_eval(concurrent=n)` lanes) share this engine and must not share partial sums, and a captured hipGraph keeps the pointer."""
-        if self.matmul != "bf16x3":
-            return 0
         c, need = self.cfg, 0
         for k, n in ((c.d_model, 3 * c.d_model), (c.d_model, c.d_model), (c.d_model, c.d_ff), (c.d_ff, c.d_model)):
-            if n % 64 == 0 and 3 * k >= 4096:
+            if self.matmul == "f32":
+                need = max(need, int(self._L.lmrl_sgemm_ws_bytes(rows, n, k, 1)))
+            elif n % 64 == 0 and 3 * k >= 4096:
                 need = max(need, int(self._L.lmrl_gemm_bf16_splitk_ws_bytes(rows, n, 3 * k)))
         return need
 
     def linear(self, x, rows, k, n, w_name, p, y, scratch, gelu_split=None, splitk_ws=None):
         """y[rows][n] = x[rows][k] @ W + b for a layer's Dense `w_name` in this engine's matmul mode (`scratch`: bf16 [rows][3 k] split buffer).
         bf16x3 with `gelu_split` (a bf16 buffer of >= rows * 3 n elements): gelu_new(y) is written there as a split operand instead of y.
-        `splitk_ws`: the caller's uint8 workspace of >= `splitk_ws_bytes(rows)` bytes (see there); without one the long-K products run unsplit."""
+        `splitk_ws`: the caller's uint8 workspace of >= `splitk_ws_bytes(rows)` bytes (see there); without one, bf16x3's long-K products run
+        unsplit and f32's take a workspace from torch's caching allocator (`ops.sgemm`)."""
         if self.matmul == "f32":
-            ops.sgemm(x, p[w_name + ".weight"], y, rows, n, k, lda=k, ldb=n, ldc=n, bias=p[w_name + ".bias"])
+            ops.sgemm(x, p[w_name + ".weight"], y, rows, n, k, lda=k, ldb=n, ldc=n, bias=p[w_name + ".bias"], ws=splitk_ws)
             return
         L = self._L
         if x is not None:          # None: `scratch` already holds the split operand (written by the producing LayerNorm / gelu launch)
@@ -120,6 +121,9 @@ class KVSessionF32:
         self.token = t.zeros(batch, dtype=t.int32, device=dev)
         self.logprob = t.zeros(batch, dtype=t.float32, device=dev)
         self.logits = t.zeros(batch, c.vocab_padded, dtype=t.float32, device=dev)
+        if eng.matmul == "bf16x3":     # the LM head's split operand and the fused sampler's workspace (zero-filled once: work-list heads)
+            self._lm_split = t.empty(batch * 3 * c.d_model, dtype=t.bfloat16, device=dev)
+            self._sample_ws = t.zeros(eng._L.lmrl_sample_ws_bytes(batch, c.vocab_padded), dtype=t.uint8, device=dev)
         self._ws = {}
         self._len_bound = 0
 
@@ -128,15 +132,16 @@ class KVSessionF32:
         t = torch
         if C not in self._ws:
             c, R, dev = self.eng.cfg, self.B * C, self.eng.device
+            nsk = self.eng.splitk_ws_bytes(R)
             f = lambda *s: t.empty(*s, dtype=t.float32, device=dev)
             self._ws[C] = dict(ids=t.zeros(R, dtype=t.int32, device=dev), pos=t.zeros(R, dtype=t.int32, device=dev), x=f(R, c.d_model), h=f(R, c.d_model),
                                r=f(R, c.d_model),
                                qkv=f(R, 3 * c.d_model), att=f(R, c.d_model), ff=f(R, c.d_ff), mean=f(R), rstd=f(R),
                                split=t.zeros(R * 3 * c.d_model, dtype=t.bfloat16, device=dev) if self.eng.matmul == "bf16x3" else None,
                                split2=t.zeros(R * 3 * c.d_ff, dtype=t.bfloat16, device=dev) if self.eng.matmul == "bf16x3" else None,
-                               # split-K partial sums of THIS session's long-K products: per session and per chunk size, sized once here (never
+                               # split-K partial sums of THIS session's products: per session and per chunk size, sized once here (never
                                # reallocated: captured graphs hold the pointer; never shared: lanes on other streams own theirs)
-                               splitk=t.empty(self.eng.splitk_ws_bytes(R), dtype=t.uint8, device=dev) if self.eng.splitk_ws_bytes(R) else None)
+                               splitk=t.empty(nsk, dtype=t.uint8, device=dev) if nsk else None)
         return self._ws[C]
 
     def reset(self):
@@ -158,6 +163,7 @@ class KVSessionF32:
         ops.embed_fwd(e.wte, e.wpe, w["ids"], w["pos"], x, R, d, vocab=c.vocab_padded)     # rows >= cfg.vocab of the engine table are zero; dead slots carry id 0
         r, pending = w["r"], None              # residual adds ride in the LayerNorm launch behind them (lmrl_layernorm_add_fwd: x += pending, then LN)
         x3 = e.matmul == "bf16x3" and d % 256 == 0 and d <= 1280      # bf16x3: LayerNorm / gelu write the three-term split operand themselves
+        sk = w["splitk"] if e.matmul == "f32" else None                # (bf16x3 splits K of the MLP's c_proj only)
 
         def ln(resid, g, b):
             if x3:
@@ -167,17 +173,17 @@ class KVSessionF32:
             ops.layernorm_add_fwd(x, resid, g, b, h, w["mean"], w["rstd"], None, 0, R, d, c.ln_eps)
             return h
         for l, p in enumerate(e.layers):
-            e.linear(ln(pending, p["ln_1.weight"], p["ln_1.bias"]), R, d, 3 * d, "attn.c_attn", p, qkv, w["split"])
+            e.linear(ln(pending, p["ln_1.weight"], p["ln_1.bias"]), R, d, 3 * d, "attn.c_attn", p, qkv, w["split"], splitk_ws=sk)
             # (bf16x3: the attention lanes that hold the output also write it as the projection GEMM's split operand — no split pass)
             _lib.check(L.lmrl_attn_cached_f32_split3(_lib.ptr(qkv), _lib.ptr(self.kv[l, 0]), _lib.ptr(self.kv[l, 1]), _lib.ptr(self.len), _lib.ptr(cnt),
                                                      _lib.ptr(att), _lib.ptr(w["split"]) if x3 else None, B, C, c.n_head, self.tmax, sp), "lmrl_attn_cached_f32")
-            e.linear(None if x3 else att, R, d, d, "attn.c_proj", p, r, w["split"])   # r = att . Wproj + b ; x += r inside the ln_2 launch
+            e.linear(None if x3 else att, R, d, d, "attn.c_proj", p, r, w["split"], splitk_ws=sk)   # r = att . Wproj + b ; x += r inside the ln_2 launch
             if x3:
                 # c_fc reads the LayerNorm's split operand (w["split"], pitch 3 d) and writes gelu's split operand (w["split2"], pitch 3 d_ff)
                 e.linear(ln(r, p["ln_2.weight"], p["ln_2.bias"]), R, d, c.d_ff, "mlp.c_fc", p, None, w["split"], gelu_split=w["split2"])
                 e.linear(None, R, c.d_ff, d, "mlp.c_proj", p, r, w["split2"], splitk_ws=w["splitk"])
             else:
-                e.linear(ln(r, p["ln_2.weight"], p["ln_2.bias"]), R, d, c.d_ff, "mlp.c_fc", p, ff, w["split"])
+                e.linear(ln(r, p["ln_2.weight"], p["ln_2.bias"]), R, d, c.d_ff, "mlp.c_fc", p, ff, w["split"], splitk_ws=sk)
                 ops.gelu_fwd(ff, ff)
                 e.linear(ff, R, c.d_ff, d, "mlp.c_proj", p, r, w["split2"], splitk_ws=w["splitk"])         # r = mlp output ; added by the next LayerNorm launch
             pending = r
@@ -205,9 +211,6 @@ class KVSessionF32:
         if e.matmul == "f32":
             ops.sgemm(h, e.wte, self.logits, self.B, c.vocab_padded, c.d_model, trans_b=True, lda=c.d_model, ldb=c.d_model, ldc=c.vocab_padded)
         else:
-            import torch
-            if getattr(self, "_lm_split", None) is None:
-                self._lm_split = torch.empty(self.B * 3 * c.d_model, dtype=torch.bfloat16, device=e.device)
             _lib.check(e._L.lmrl_split3_bf16(h.data_ptr(), c.d_model, self.B, c.d_model, self._lm_split.data_ptr(), 3 * c.d_model, _lib.stream_ptr()), "lmrl_split3_bf16")
             _lib.check(e._L.lmrl_gemm_bf16(self._lm_split.data_ptr(), e.wte_x3.data_ptr(), None, self.logits.data_ptr(), self.B, c.vocab_padded, 3 * c.d_model,
                                            3 * c.d_model, c.vocab_padded, c.vocab_padded, 3, _lib.stream_ptr()), "lmrl_gemm_bf16 (bf16x3 LM head)")
@@ -223,11 +226,7 @@ class KVSessionF32:
             # the LM head and the sampler in ONE launch (`lm_head_sample_kernel`, the bf16 engine's): the tied-head product runs as a bf16 GEMM over
             # K' = 3 d on the split operands and the Gumbel-max / arg-max epilogue reads the fp32 accumulators — no [B][V] fp32 logits written and
             # re-read per token (2 x 206 MB at B = 1024), same random streams (Philox or LMRL_RNG_JAX: keyed by row / column / step, not by K)
-            import torch
             h = self.last_hidden if hidden is None else hidden
-            if getattr(self, "_lm_split", None) is None:
-                self._lm_split = torch.empty(self.B * 3 * c.d_model, dtype=torch.bfloat16, device=e.device)
-                self._sample_ws = torch.zeros(e._L.lmrl_sample_ws_bytes(self.B, c.vocab_padded), dtype=torch.uint8, device=e.device)   # zero-filled once (work-list heads)
             _lib.check(e._L.lmrl_split3_bf16(h.data_ptr(), c.d_model, self.B, c.d_model, self._lm_split.data_ptr(), 3 * c.d_model, _lib.stream_ptr()), "lmrl_split3_bf16")
             _lib.check(e._L.lmrl_lm_head_sample(_lib.ptr(self._lm_split), _lib.ptr(e.wte_x3), None, None, None, None, None, None, self.B, 3 * c.d_model, c.vocab,
                                                 c.vocab_padded, ctypes.byref(params), _lib.ptr(steer_tok), _lib.ptr(active), _lib.ptr(self.token),

@@ -18,12 +18,21 @@ def _sp():
 
 
 def sgemm(a, b, c, m, n, k, *, trans_a=False, trans_b=False, alpha=1.0, beta=0.0, lda=None, ldb=None, ldc=None,
-          a_off=0, b_off=0, c_off=0, batch=(1, 1), sa=(0, 0), sb=(0, 0), sc=(0, 0), bias=None):
-    """C = alpha*op(A).op(B) + beta*C (+bias); offsets / strides in ELEMENTS; batch = (outer, inner)."""
+          a_off=0, b_off=0, c_off=0, batch=(1, 1), sa=(0, 0), sb=(0, 0), sc=(0, 0), bias=None, ws=None):
+    """C = alpha*op(A).op(B) + beta*C (+bias); offsets / strides in ELEMENTS; batch = (outer, inner).
+    ws: split-K workspace of >= lmrl_sgemm_ws_bytes bytes.  Without one, a product that splits takes its workspace from torch's caching
+    allocator for this call: the block is stream-ordered (reused only after the reduce that reads it has run) and, during a graph capture,
+    comes from the graph's private pool, which lives as long as the graph."""
     es = 4
+    if ws is None:
+        nb = _L().lmrl_sgemm_ws_bytes(m, n, k, batch[0] * batch[1])
+        if nb:
+            import torch
+            ws = torch.empty(nb, dtype=torch.uint8, device=c.device)
     _lib.check(_L().lmrl_sgemm(int(trans_a), int(trans_b), m, n, k, float(alpha), a.data_ptr() + a_off * es, lda, sa[0], sa[1],
                                b.data_ptr() + b_off * es, ldb, sb[0], sb[1], float(beta), c.data_ptr() + c_off * es, ldc, sc[0], sc[1],
-                               batch[0], batch[1], _lib.ptr(bias), _sp()), "lmrl_sgemm")
+                               batch[0], batch[1], _lib.ptr(bias), _lib.ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _sp()),
+               "lmrl_sgemm")
 
 
 def _pad(n: int, m: int = 64) -> int:

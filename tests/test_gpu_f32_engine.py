@@ -205,17 +205,19 @@ def test_f32_engines_graph_replay_is_bit_identical_to_eager(dev, matmul):
     ro.close()
 
 
-def test_bf16x3_lanes_own_their_split_k_workspace(dev):
-    """the split-K partial sums of the bf16x3 c_proj products used to live on the ENGINE, which `text_env_eval(concurrent=n)`
-    lanes share across HIP streams — one lane's reduce could read the other's partials.  They belong to the session now (sized once per chunk
-    size, before any capture).  Greedy episodes are noise-independent, so the same batches must come back bit-identical from one lane and from
-    two lanes in flight, on a width whose c_proj takes the split-K path at decode AND chunk size."""
+@pytest.mark.parametrize("matmul", ["f32", "bf16x3"])
+def test_bf16x3_lanes_own_their_split_k_workspace(dev, matmul):
+    """the split-K partial sums of the bf16x3 c_proj products used to live on the ENGINE, and those of the f32 products in
+    one process-wide buffer of `lmrl_sgemm`, which `text_env_eval(concurrent=n)` lanes share across HIP streams — one lane's reduce could read
+    the other's partials.  They belong to the session now (sized once per chunk size, before any capture).  Greedy episodes are
+    noise-independent, so the same batches must come back bit-identical from one lane and from two lanes in flight, on a width whose c_proj
+    takes the split-K path at decode AND chunk size."""
     from lmrl_gym_amd.envs import wordle as W
     from lmrl_gym_amd.gpt2 import GPT2Config, init_hf_style_state_dict
     from lmrl_gym_amd.gpt2_f32_engine import GPT2EngineF32
     from lmrl_gym_amd.rollout import WordleRolloutEngine
     cfg = GPT2Config(2, 4, 256, 2048, 50257, 128)
-    eng = GPT2EngineF32(cfg, init_hf_style_state_dict(cfg, seed=2), dev, matmul="bf16x3")
+    eng = GPT2EngineF32(cfg, init_hf_style_state_dict(cfg, seed=2), dev, matmul=matmul)
     B = 256
     assert eng.splitk_ws_bytes(B) > 0 and eng.splitk_ws_bytes(8 * B) > 0 and not hasattr(eng, "_splitk_ws")
     vocab = W.Vocabulary.builtin("wordle_official_400.txt")
@@ -227,4 +229,59 @@ def test_bf16x3_lanes_own_their_split_k_workspace(dev):
     assert len(ro._lanes) == 3 and one == two == three and s1 == s2
     ws = [e.ses._ws[c]["splitk"].data_ptr() for e, _ in ro._lanes for c in sorted(e.ses._ws)]
     assert len(set(ws)) == len(ws)                        # every lane / chunk size has its own partial-sum buffer
+    ro.close()
+
+
+def test_f32_episode_graph_survives_a_train_step_in_the_same_process(dev):
+    """A captured fp32 episode records the split-K workspace of its decode / chunk products.  A fp32 train step in the same process needs far
+    more partial sums for its weight gradients (K = B*T rows); when the workspace was one process-wide buffer, that step freed and regrew it
+    under the captured graph.  Now the graph holds the session's own workspace: replaying after the train step gives the same trajectory and
+    the same last logits, bit for bit, as replaying before it with the same seeds, guesses and epoch word."""
+    from lmrl_gym_amd.envs import wordle as W
+    from lmrl_gym_amd.gpt2 import GPT2Config, init_hf_style_state_dict
+    from lmrl_gym_amd.gpt2_f32_engine import GPT2EngineF32
+    from lmrl_gym_amd.rollout import WordleRolloutEngine
+    from lmrl_gym_amd.train import ops
+    from lmrl_gym_amd.train.gpt2_f32 import GPT2F32
+    cfg = GPT2Config(2, 4, 256, 1024, 50257, 128)
+    sd = init_hf_style_state_dict(cfg, seed=1)
+    eng = GPT2EngineF32(cfg, sd, dev, matmul="f32")
+    vocab = W.Vocabulary.builtin("wordle_official_400.txt")
+    B = 192
+    ro = WordleRolloutEngine(eng, vocab, B, max_new_tokens=6, bad_word_reward=-10.0)
+    rng = np.random.RandomState(3)
+    packed = np.array([W.pack_guess(w) for w in vocab.all_vocab], dtype=np.uint32)
+    guesses = torch.from_numpy(packed[rng.randint(0, len(packed), size=(6, B))].view(np.int32)).to(dev)
+    seeds = (torch.arange(B, dtype=torch.int64) + 900).to(dev)
+    ro.capture_episode(scripted=True, temperature=1.0, sample_seed=11, steer_strength=12.5)
+    epoch = ro.g_epoch.clone()
+
+    def replay():
+        ro.g_epoch.copy_(epoch)                   # replay_episode advances the epoch word by one: both replays draw the same noise
+        ro.replay_episode(seeds, guesses)
+        out = {k: v.clone() for k, v in ro.traj.items()}
+        out["logits"] = ro.ses.logits.clone()
+        return out
+    before = replay()
+    ws = max(eng.splitk_ws_bytes(B * c) for c in ro.ses._ws)
+    assert ws > 0
+
+    # one fp32 forward + backward at K = 16 x 128 = 2048 rows: its weight gradients split K into more partial sums than the session holds
+    Bt, T = 16, 128
+    d, ff = cfg.d_model, cfg.d_ff
+    assert max(ops._L().lmrl_sgemm_ws_bytes(m, n, Bt * T, 1) for m, n in ((d, 3 * d), (d, d), (d, ff), (ff, d))) > ws
+    pol = GPT2F32({k: v.clone() for k, v in sd.items()}, cfg.n_head, device=dev)
+    g = torch.Generator().manual_seed(5)
+    ids = torch.randint(0, cfg.vocab, (Bt, T), generator=g, dtype=torch.int32).to(dev)
+    pos = torch.arange(T, dtype=torch.int32).expand(Bt, T).contiguous().to(dev)
+    hid, cache = pol.forward(ids, torch.ones(Bt, T, dtype=torch.uint8, device=dev), pos)
+    grads = pol.zero_grads()
+    pol.backward(cache, torch.randn(Bt * T, d, generator=g).to(dev), grads)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(grads.flat).all()) and float(grads.flat.abs().max()) > 0
+    del hid, cache, grads
+    after = replay()
+    for k in before:
+        assert torch.equal(before[k], after[k]), k
+    assert int(before["n_steps"].sum()) > 3 * B
     ro.close()

@@ -39,21 +39,30 @@ def test_sgemm_all_layouts(dev, ta, tb):
 
 
 def test_sgemm_split_k_weight_gradient_shapes(dev):
-    """dW = X^T dY shapes (small M x N, K = all tokens): the split-K path must equal a float64 matmul and be bit-reproducible."""
+    """dW = X^T dY shapes (small M x N, K = all tokens): the split-K path must equal a float64 matmul and be bit-reproducible.  The caller's
+    workspace (lmrl_sgemm_ws_bytes) gives the same bits as ops.sgemm's own; one float less is refused before anything is launched."""
+    from lmrl_gym_amd import _lib
     from lmrl_gym_amd.train import ops
     g = torch.Generator().manual_seed(11)
     for (ta, tb, M, N, K) in [(1, 0, 256, 384, 8192), (0, 1, 128, 256, 4096), (0, 0, 200, 130, 16384)]:
         A = torch.randn((K, M) if ta else (M, K), generator=g); B = torch.randn((N, K) if tb else (K, N), generator=g)
         C0 = torch.randn(M, N, generator=g); bias = torch.randn(N, generator=g)
         ref = 0.5 * ((A.t() if ta else A).double() @ (B.t() if tb else B).double()) + 1.0 * C0.double() + bias.double()
+        Ad, Bd, bd = A.to(dev), B.to(dev), bias.to(dev)
+        nws = ops._L().lmrl_sgemm_ws_bytes(M, N, K, 1)
+        assert nws > 0
         outs = []
-        for _ in range(2):
+        for ws in (None, None, torch.empty(nws, dtype=torch.uint8, device=dev)):
             Cd = C0.to(dev).clone()
-            ops.sgemm(A.to(dev), B.to(dev), Cd, M, N, K, trans_a=bool(ta), trans_b=bool(tb), alpha=0.5, beta=1.0, lda=A.shape[1],
-                      ldb=B.shape[1], ldc=N, bias=bias.to(dev))
+            ops.sgemm(Ad, Bd, Cd, M, N, K, trans_a=bool(ta), trans_b=bool(tb), alpha=0.5, beta=1.0, lda=A.shape[1], ldb=B.shape[1], ldc=N,
+                      bias=bd, ws=ws)
             outs.append(Cd.cpu())
-        assert torch.equal(outs[0], outs[1])
+        assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
         _close(outs[0], ref, rtol=3e-6, name=f"splitk {M}x{N}x{K}")
+        with pytest.raises(_lib.LmrlError, match="workspace"):
+            ops.sgemm(Ad, Bd, Cd, M, N, K, trans_a=bool(ta), trans_b=bool(tb), alpha=0.5, beta=1.0, lda=A.shape[1], ldb=B.shape[1], ldc=N,
+                      bias=bd, ws=torch.empty(nws - 4, dtype=torch.uint8, device=dev))
+        assert torch.equal(Cd.cpu(), outs[2])
 
 
 def test_sgemm_batched_strided_like_attention(dev):

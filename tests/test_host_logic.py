@@ -50,6 +50,39 @@ def test_cabi_library_exports_every_declared_symbol():
     assert L.lmrl_version() >= 100
 
 
+# (m, n, k, batch) -> split-K workspace bytes; S = bytes / (4 m n) slices.  Derived from the cost-model loop as it stood when the
+# workspace was a process-wide buffer inside lmrl_sgemm, not from lmrl_sgemm_ws_bytes: moving the plan into one function kept it.
+_SGEMM_WS_BYTES = [
+    ((1024, 2304, 768, 1), 28311552),       # fp32 decode at B = 1024, d = 768: c_attn, S = 3
+    ((1024, 768, 768, 1), 15728640),        # c_proj, S = 5
+    ((1024, 3072, 768, 1), 0),              # c_fc: 192 tiles
+    ((1024, 768, 3072, 1), 15728640),       # fc2, S = 5
+    ((768, 2304, 16384, 1), 49545216),      # dW at K = 16 384 rows: c_attn, S = 7
+    ((768, 768, 16384, 1), 16515072),       # c_proj, S = 7
+    ((768, 3072, 16384, 1), 66060288),      # c_fc, S = 7
+    ((3072, 768, 16384, 1), 66060288),      # fc2, S = 7
+    ((256, 256, 2048, 1), 4194304),         # d = 256, B = 256 c_proj of the MLP, S = 16
+    ((64, 768, 16384, 1), 0),               # m < 128
+    ((4096, 768, 3072, 1), 0),              # m > 2048 at K < 4096
+    ((1024, 768, 3072, 2), 0),              # batched
+    ((1024, 50304, 768, 1), 0),             # vocabulary head
+]
+
+
+def test_sgemm_split_k_workspace_plan():
+    """lmrl_sgemm_ws_bytes is host arithmetic (no device): the split-K plan pinned on the fp32 engine's and the train step's shapes, and the
+    64 x 64 A/B variant, which never splits, taking the same plan function."""
+    from lmrl_gym_amd import _lib
+    L = _lib.lib()
+    for (m, n, k, batch), nbytes in _SGEMM_WS_BYTES:
+        assert L.lmrl_sgemm_ws_bytes(m, n, k, batch) == nbytes, (m, n, k, batch)
+    L.lmrl_sgemm_set_variant(1)
+    try:
+        assert all(L.lmrl_sgemm_ws_bytes(*shape) == 0 for shape, _ in _SGEMM_WS_BYTES)
+    finally:
+        L.lmrl_sgemm_set_variant(0)
+
+
 # ------------------------------------------------------------------ MT19937 core (device code built for the host)
 def test_device_mt19937_core_matches_cpython():
     L = _host_lib()

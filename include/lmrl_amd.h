@@ -531,6 +531,8 @@ int lmrl_sample_logits_steer(float *logits_d, int ld, int m, int vocab, const lm
  * fp32 rollout mode (csrc/attn_cached_f32.hip + the fp32 train-step kernels below): the reference's DEFAULT rollout arithmetic is float32
  * (llm_rl_scripts/wordle/bc/eval_bc_gpt2.py:34,69); `lmrl_gym_amd.gpt2_f32_engine.GPT2EngineF32` sequences these calls — lmrl_embed_fwd,
  * lmrl_layernorm_fwd, lmrl_sgemm (exact fp32 MFMA), lmrl_gelu_fwd — around an fp32 K/V cache.
+ * Its value policies (ILQL / MC) take their LM head from lmrl_value_head_logits_f32 (below, with lmrl_sgemm) in "f32" mode and from
+ * lmrl_lm_head_sample on three split operands in "bf16x3" mode.
  *   lmrl_chunk_begin_f32  pos[b*c + j] = len[b] + j for j < cnt[b]; padding slots get position 0 and token id 0
  *   lmrl_attn_cached_f32  one layer's attention for the c new tokens of every env: qkv_d fp32 [b*c][3*H*64]; kcache_d / vcache_d fp32
  *                         [b][tmax][H*64]; query j sees the cached positions [0, len[b]) and the chunk's tokens [0, j]; appends the new
@@ -741,6 +743,15 @@ int lmrl_sgemm(int trans_a, int trans_b, int m, int n, int k, float alpha, const
                long sa_inner, const float *b_d, int ldb, long sb_outer, long sb_inner, float beta, float *c_d, int ldc,
                long sc_outer, long sc_inner, int nb_outer, int nb_inner, const float *bias_d, void *ws_d, size_t ws_bytes,
                void *stream);
+/* The value policy's LM head in exact fp32 (csrc/value_head_f32.hip; value_rl_base/gpt2/generation.py:100-119), element by element:
+ *   pi = h . wte^T    q_i = qh_i . w2_i^T + b2_i    logits = fmaf(beta, qh2 ? fminf(q1, q2) : q1, pi)
+ * h_d, qh{1,2}_d fp32 [m][d]; wte_d, w2_{1,2}_d fp32 [vocab_padded][d] ([out][in]); b2_{1,2}_d fp32 [vocab_padded]; logits_d fp32 [m][ld].
+ * qh2_d, w2_2_d, b2_2_d all NULL: the MC-returns policy (no Q2).  Each product is bit-equal to lmrl_sgemm of the same operands (+ bias);
+ * only the combined logits are written.  d % 64 == 0, vocab_padded % 128 == 0, ld >= vocab_padded, any m > 0; h / wte / qh / w2 16-byte
+ * aligned.  No workspace, no device state: deterministic and capturable. */
+int lmrl_value_head_logits_f32(const float *h_d, const float *wte_d, const float *qh1_d, const float *w2_1_d, const float *b2_1_d,
+                               const float *qh2_d, const float *w2_2_d, const float *b2_2_d, float beta, int m, int d, int vocab_padded,
+                               float *logits_d, int ld, void *stream);
 /* A/B hook: 0 = auto (128x128 tiles when m, n >= 128, split K as above), 1 = always the 64x64-tile kernel, never split
  * (lmrl_sgemm_ws_bytes follows the setting) */
 void lmrl_sgemm_set_variant(int v);

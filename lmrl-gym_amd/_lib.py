@@ -131,6 +131,7 @@ _SIGS = {
                            ctypes.c_long, ctypes.c_long, c_float, c_void_p, c_int, ctypes.c_long, ctypes.c_long, c_int, c_int, c_void_p, c_void_p, c_size_t,
                            c_void_p]),
     "lmrl_sgemm_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "lmrl_value_head_logits_f32": (c_int, [c_void_p] * 8 + [c_float, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "lmrl_embed_fwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
     "lmrl_cast_bf16": (c_int, [c_void_p, ctypes.c_long, c_int, c_int, c_void_p, ctypes.c_long, c_int, c_int, c_void_p]),
     "lmrl_cast_bf16_segments": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

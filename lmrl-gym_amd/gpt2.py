@@ -154,6 +154,27 @@ class GPT2Engine:
     def session(self, batch: int, tmax: int, flags: int = 0) -> "KVSession":
         return KVSession(self, batch, tmax, flags)
 
+    # ---- the value policy's Q heads on this engine (`policies.heads_to_engine_layout` dicts: bf16 w1 / w2, f32 b1 / b2)
+    def check_value_head(self, head: dict) -> None:
+        """Raise unless `head` is a bf16-engine head (`heads_to_engine_layout` without an fp32 engine)."""
+        import torch
+        if "layout" in head or head["w2"].dtype != torch.bfloat16:
+            raise _lib.LmrlError(f"value head laid out for a GPT2EngineF32 ({head.get('layout')}), not for the bf16 GPT2Engine")
+
+    def q_hidden_buffer(self, rows: int):
+        """Output buffer of `q_hidden` for `rows` rows (bf16 [rows][d], the fused sampler's Q operand)."""
+        import torch
+        return torch.zeros(rows, self.cfg.d_model, dtype=torch.bfloat16, device=self.device)
+
+    def q_hidden_ws(self, rows: int):
+        return None
+
+    def q_hidden(self, head: dict, x, out, ws=None):
+        """out bf16 [rows][d] = relu(x . W1 + b1) of a Q head's dense1 on bf16 hidden states x."""
+        d = self.cfg.d_model
+        _lib.check(self._L.lmrl_gemm_bf16(_lib.ptr(x), _lib.ptr(head["w1"]), _lib.ptr(head["b1"]), _lib.ptr(out), x.shape[0], d, d, d, d, d,
+                                          4, _lib.stream_ptr()), "lmrl_gemm_bf16(q head dense1 + relu)")
+
     def __del__(self):
         try:
             if self._h:

@@ -9,7 +9,14 @@ same sampler (`lmrl_sample_logits_steer`: identical random streams, top-k / top-
 `KVSession` (reset / forward / sample / broadcast_prefix_from / last_hidden / token), so `WordleRolloutEngine`, the text policies and
 the tests drive either engine unchanged; `tests/test_gpu_f32_engine.py` compares EVERY sampled token of a rollout with the float64
 oracle.  It trades throughput for exactness (plain fp32 GEMMs at ~0.5 of the 157 TFLOP/s f32 MFMA peak; `bench.py` reports it as
-`fp32_mode`).  There is no ILQL-perturbed sampling here (the Q-head operands of the fused sampler are bf16): policy rollouts only.
+`fp32_mode`).
+
+The ILQL and MC-returns value policies (logits = pi_beta + beta * min(Q1, Q2), or + beta * Q without a Q2: value_rl_base/gpt2/generation.py:100-119)
+run here too, in the reference's default float32 (wordle/ilql/eval_ilql_gpt2.py:36, wordle/mc/eval_mc_gpt2.py).  `value_head` lays an MLP head's
+parameters out unrounded, `q_hidden` computes relu(dense1) in exact fp32 on the value base's last hidden state, and `KVSessionF32.sample(q1=, q2=)`
+takes the dense2 products: in "f32" mode one launch of `lmrl_value_head_logits_f32` (the three products and the combine on the f32 MFMA, csrc/
+value_head_f32.hip) into the materialised logits, then the same sampler; in "bf16x3" mode the fused LM-head sampler with three split operands at
+K' = 3 d.
 """
 from __future__ import annotations
 
@@ -98,6 +105,51 @@ class GPT2EngineF32:
         _lib.check(L.lmrl_gemm_bf16(scratch.data_ptr(), p[w_name + ".weight.x3"].data_ptr(), p[w_name + ".bias"].data_ptr(), y.data_ptr(), rows, n, 3 * k, 3 * k,
                                     n, n, 3, _lib.stream_ptr()), "lmrl_gemm_bf16 (bf16x3)")
 
+    def value_head(self, mlp_params: dict) -> dict:
+        """MLPHead params (`dense1.kernel` [d][d], `dense1.bias`, `dense2.kernel` [d][vocab], `dense2.bias`) -> this engine's head layout, nothing
+        rounded: fp32 `w1` [d][d] ([out][in]), `b1` [d], `w2` [vocab_padded][d] and `b2` [vocab_padded] zero-padded past the vocabulary, and in
+        bf16x3 mode `w2_x3` bf16 [vocab_padded][3 d] = [hi | hi | lo] (the layout of `wte_x3`).  `layout` names the matmul mode it serves."""
+        import torch
+        c, f32 = self.cfg, (lambda t: t.to(self.device, torch.float32))
+        w2k = mlp_params["dense2.kernel"]
+        d, V = w2k.shape
+        if d != c.d_model or V > c.vocab_padded:
+            raise _lib.LmrlError(f"value head dense2 [{d}][{V}] does not fit d_model = {c.d_model}, vocab_padded = {c.vocab_padded}")
+        w2 = torch.zeros(c.vocab_padded, d, dtype=torch.float32, device=self.device)
+        w2[:V] = f32(w2k).t()
+        b2 = torch.zeros(c.vocab_padded, dtype=torch.float32, device=self.device)
+        b2[:V] = f32(mlp_params["dense2.bias"])
+        head = dict(w1=f32(mlp_params["dense1.kernel"]).t().contiguous(), b1=f32(mlp_params["dense1.bias"]).contiguous(), w2=w2, b2=b2,
+                    layout=self.matmul)
+        if self.matmul == "bf16x3":
+            hi = w2.to(torch.bfloat16)
+            head["w2_x3"] = torch.cat([hi, hi, (w2 - hi.float()).to(torch.bfloat16)], dim=1).contiguous()
+        return head
+
+    def check_value_head(self, head: dict) -> None:
+        """Raise unless `head` was built by `value_head` of an engine in this engine's matmul mode."""
+        import torch
+        if head.get("layout") != self.matmul or head["w2"].dtype != torch.float32:
+            raise _lib.LmrlError(f"value head laid out for {head.get('layout', 'the bf16 engine')!s}, not for a GPT2EngineF32 in {self.matmul} mode "
+                                 "(build it with this engine's value_head)")
+
+    def q_hidden_buffer(self, rows: int):
+        """Output buffer of `q_hidden` for `rows` rows (fp32 [rows][d])."""
+        import torch
+        return torch.zeros(rows, self.cfg.d_model, dtype=torch.float32, device=self.device)
+
+    def q_hidden_ws(self, rows: int):
+        """Split-K workspace of one caller's `q_hidden` on `rows` rows (None: the product does not split).  Per caller, like `splitk_ws_bytes`."""
+        import torch
+        nb = int(self._L.lmrl_sgemm_ws_bytes(rows, self.cfg.d_model, self.cfg.d_model, 1))
+        return torch.empty(nb, dtype=torch.uint8, device=self.device) if nb else None
+
+    def q_hidden(self, head: dict, x, out, ws=None):
+        """out fp32 [rows][d] = relu(x . W1 + b1): a Q head's dense1 in exact fp32 (in both matmul modes — [rows][d] x [d][d] is small)."""
+        d, rows = self.cfg.d_model, x.shape[0]
+        ops.sgemm(x, head["w1"], out, rows, d, d, trans_b=True, lda=d, ldb=d, ldc=d, bias=head["b1"], ws=ws)
+        ops.relu_fwd(out, out)
+
     @classmethod
     def random_init(cls, cfg: GPT2Config, seed: int = 0, device=None, matmul: str = "f32") -> "GPT2EngineF32":
         return cls(cfg, init_hf_style_state_dict(cfg, seed), device, matmul=matmul)
@@ -124,6 +176,8 @@ class KVSessionF32:
         if eng.matmul == "bf16x3":     # the LM head's split operand and the fused sampler's workspace (zero-filled once: work-list heads)
             self._lm_split = t.empty(batch * 3 * c.d_model, dtype=t.bfloat16, device=dev)
             self._sample_ws = t.zeros(eng._L.lmrl_sample_ws_bytes(batch, c.vocab_padded), dtype=t.uint8, device=dev)
+            # the value policy's Q hiddens as split operands (sessions of one lane each own theirs)
+            self._q_split = [t.empty(batch * 3 * c.d_model, dtype=t.bfloat16, device=dev) for _ in range(2)]
         self._ws = {}
         self._len_bound = 0
 
@@ -195,6 +249,15 @@ class KVSessionF32:
         ops.layernorm_fwd(self._last_x, e.lnf_g, e.lnf_b, self.last_hidden, w["mean"], w["rstd"], B, d, c.ln_eps)
         return self.last_hidden
 
+    def set_len(self, lens):
+        """Truncate / set every env's cache length from the host (int array [B]), as `KVSession.set_len`: positions >= lens[b] are free and will be
+        overwritten by the next forwards (a policy keeps the K/V rows of the longest common prefix of consecutive prompts)."""
+        import torch
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        assert lens.shape == (self.B,) and int(lens.max(initial=0)) <= self.tmax
+        self.len.copy_(torch.from_numpy(lens))
+        self._len_bound = int(lens.max(initial=0))
+
     def broadcast_prefix_from(self, src: "KVSessionF32", n_pos: int):
         """Every env starts with the n_pos-token prefix held by the 1-env session `src` (device-to-device row copies)."""
         assert src.B == 1 and src.eng is self.eng
@@ -218,9 +281,13 @@ class KVSessionF32:
 
     def sample(self, params: SampleParams, steer_tok=None, active=None, hidden=None, logits_out=None, q1=None, q2=None, want_logprob: bool = True):
         """One token per env from `hidden` (default: last_hidden).  matmul = "f32": fp32 LM head into materialised logits, then the sampler on them
-        (same streams and warpers as the fused bf16 path); matmul = "bf16x3": the fused LM-head sampler on the split operands."""
-        if q1 is not None or q2 is not None:
-            raise _lib.LmrlError("GPT2EngineF32 samples from the policy logits only (the ILQL Q-head operands of the fused sampler are bf16)")
+        (same streams and warpers as the fused bf16 path); matmul = "bf16x3": the fused LM-head sampler on the split operands.
+        q1 (+ q2): the value policy's Q heads as (qh fp32 [B][d] = `GPT2EngineF32.q_hidden`, w2, b2 fp32 [vocab_padded]) with w2 a `value_head`'s
+        `w2` (f32 mode) or `w2_x3` (bf16x3 mode): logits = pi_beta + params.beta * min(Q1, Q2) (+ beta * Q1 without q2); `logits_out` gets them."""
+        if q1 is None and q2 is not None:
+            raise _lib.LmrlError("KVSessionF32.sample: q2 without q1")
+        if q1 is not None:
+            return self._sample_value(params, steer_tok, active, hidden, logits_out, q1, q2, want_logprob)
         c, e = self.eng.cfg, self.eng
         if e.matmul == "bf16x3":
             # the LM head and the sampler in ONE launch (`lm_head_sample_kernel`, the bf16 engine's): the tied-head product runs as a bf16 GEMM over
@@ -239,4 +306,39 @@ class KVSessionF32:
                                                         _lib.stream_ptr()), "lmrl_sample_logits_steer")
         if logits_out is not None:
             logits_out.copy_(lg)           # (after the steer offset, as the fused path reports its combined logits)
+        return self.token, (self.logprob if want_logprob else None)
+
+    def _sample_value(self, params, steer_tok, active, hidden, logits_out, q1, q2, want_logprob):
+        import torch
+        c, e, sp = self.eng.cfg, self.eng, _lib.stream_ptr()
+        d, Vp, h = c.d_model, c.vocab_padded, self.last_hidden if hidden is None else hidden
+        ops_ = [q for q in (q1, q2) if q is not None]
+        wdt, wk = (torch.float32, d) if e.matmul == "f32" else (torch.bfloat16, 3 * d)
+        for qh, w2, b2 in ops_:
+            if (qh.dtype != torch.float32 or tuple(qh.shape) != (self.B, d) or w2.dtype != wdt or tuple(w2.shape) != (Vp, wk)
+                    or b2.dtype != torch.float32 or b2.numel() != Vp):
+                raise _lib.LmrlError(f"KVSessionF32.sample ({e.matmul}): Q operands must be qh fp32 [{self.B}][{d}], w2 {wdt} [{Vp}][{wk}], "
+                                     f"b2 fp32 [{Vp}] (GPT2EngineF32.q_hidden / value_head)")
+        if e.matmul == "f32":
+            # the three products and the combine in one launch into the materialised logits, then the policy path's sampler on them
+            _lib.check(e._L.lmrl_value_head_logits_f32(_lib.ptr(h), _lib.ptr(e.wte), _lib.ptr(q1[0]), _lib.ptr(q1[1]), _lib.ptr(q1[2]),
+                                                       _lib.ptr(q2[0] if q2 else None), _lib.ptr(q2[1] if q2 else None), _lib.ptr(q2[2] if q2 else None),
+                                                       float(params.beta), self.B, d, Vp, _lib.ptr(self.logits), Vp, sp), "lmrl_value_head_logits_f32")
+            _lib.check(e._L.lmrl_sample_logits_steer(_lib.ptr(self.logits), Vp, self.B, c.vocab, ctypes.byref(params), _lib.ptr(steer_tok),
+                                                     _lib.ptr(active), _lib.ptr(self.token), _lib.ptr(self.logprob) if want_logprob else None, sp),
+                       "lmrl_sample_logits_steer")
+            if logits_out is not None:
+                logits_out.copy_(self.logits)
+            return self.token, (self.logprob if want_logprob else None)
+        # bf16x3: the fused LM-head sampler with three operands at K' = 3 d — every hidden split [hi | lo | hi] against weights staged [hi | hi | lo]
+        srcs = [h] + [q[0] for q in ops_]
+        dsts = [self._lm_split] + self._q_split[: len(ops_)]
+        for x, y in zip(srcs, dsts):
+            _lib.check(e._L.lmrl_split3_bf16(x.data_ptr(), d, self.B, d, y.data_ptr(), 3 * d, sp), "lmrl_split3_bf16")
+        s1, s2 = self._q_split
+        _lib.check(e._L.lmrl_lm_head_sample(_lib.ptr(self._lm_split), _lib.ptr(e.wte_x3), _lib.ptr(s1), _lib.ptr(q1[1]), _lib.ptr(q1[2]),
+                                            _lib.ptr(s2) if q2 else None, _lib.ptr(q2[1]) if q2 else None, _lib.ptr(q2[2]) if q2 else None,
+                                            self.B, 3 * d, c.vocab, Vp, ctypes.byref(params), _lib.ptr(steer_tok), _lib.ptr(active), _lib.ptr(self.token),
+                                            _lib.ptr(self.logprob) if want_logprob else None, _lib.ptr(logits_out), _lib.ptr(self._sample_ws), sp),
+                   "lmrl_lm_head_sample (bf16x3, value policy)")
         return self.token, (self.logprob if want_logprob else None)

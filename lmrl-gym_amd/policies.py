@@ -195,11 +195,13 @@ class GPT2PPOPolicy(BatchedTextPolicy):
 class GPT2ValuePolicy(GPT2PPOPolicy):
     """ILQL policy: logits = pi_beta_logits + beta * min(Q1, Q2)(h_value)   (value_rl_base/gpt2/generation.py:97-119).
 
-    q heads: dicts with bf16 device tensors `w1` [d][d] ([out][in]), `w2` [vocab_padded][d] and f32 `b1` [d], `b2` [vocab_padded]
-    (build them with `heads_to_engine_layout`)."""
+    q heads: `heads_to_engine_layout(..., engine=pi_beta)` dicts — for `GPT2Engine`s bf16 device tensors `w1` [d][d] ([out][in]), `w2`
+    [vocab_padded][d] and f32 `b1` [d], `b2` [vocab_padded]; for `GPT2EngineF32`s the engine's unrounded `value_head` layout.  q2_head=None is the
+    MC-returns policy (pi_beta + beta * Q).  pi_beta and the value base are engines of one class (and one matmul mode)."""
 
     def __init__(self, pi_beta: GPT2Engine, value_base: GPT2Engine, q1_head: dict, q2_head: Optional[dict], beta: float, tokenizer, **kw):
         super().__init__(pi_beta, tokenizer, **kw)
+        check_value_policy(pi_beta, value_base, (q1_head, q2_head))
         self.value_base, self.q1, self.q2, self.beta = value_base, q1_head, q2_head, beta
 
     def _engines(self):
@@ -209,31 +211,47 @@ class GPT2ValuePolicy(GPT2PPOPolicy):
         """ValueRLPolicy.set_params (value_rl_base/gpt2/interface.py:322-330): `(pi_beta, base, q1_head, q2_head)` — engines for
         the two transformers, `heads_to_engine_layout` dicts for the heads."""
         pi_beta, base, q1, q2 = policy_params
+        check_value_policy(pi_beta, base, (q1, q2))
         self.engine, self.value_base, self.q1, self.q2 = pi_beta, base, q1, q2
         self._gen = None
 
     def _sample(self, gen, params, active_d, logits_out):
-        import torch
-        L = _lib.lib()
         pi_ses, v_ses = gen.sessions
-        d, B = self.value_base.cfg.d_model, gen.B
+        vb = self.value_base
+        if getattr(gen, "qh", None) is None:       # the Q hiddens (and dense1's split-K workspace) of this generator's batch
+            gen.qh, gen.q_ws = [vb.q_hidden_buffer(gen.B) for _ in range(2)], vb.q_hidden_ws(gen.B)
         ops = []
-        for head in (self.q1, self.q2):
+        for i, head in enumerate((self.q1, self.q2)):
             if head is None:
                 ops.append(None)
                 continue
-            qh = torch.empty(B, d, dtype=torch.bfloat16, device=gen.dev)
-            _lib.check(L.lmrl_gemm_bf16(_lib.ptr(v_ses.last_hidden), _lib.ptr(head["w1"]), _lib.ptr(head["b1"]), _lib.ptr(qh), B, d, d, d, d, d,
-                                        4, _lib.stream_ptr()), "lmrl_gemm_bf16(q head dense1 + relu)")
-            ops.append((qh, head["w2"], head["b2"]))
+            vb.q_hidden(head, v_ses.last_hidden, gen.qh[i], gen.q_ws)
+            ops.append((gen.qh[i], head.get("w2_x3", head["w2"]), head["b2"]))
         params.beta = self.beta
         return pi_ses.sample(params, active=active_d, logits_out=logits_out, q1=ops[0], q2=ops[1], want_logprob=False)
 
 
-def heads_to_engine_layout(head_params: dict, vocab_padded: int, device) -> dict:
+def check_value_policy(pi_beta, value_base, heads) -> None:
+    """Raise `LmrlError` unless pi_beta and the value base are engines of one class and one matmul mode and every head dict was laid out for
+    that kind of engine (`heads_to_engine_layout` with such an engine)."""
+    if type(pi_beta) is not type(value_base):
+        raise _lib.LmrlError(f"value policy: pi_beta is a {type(pi_beta).__name__}, the value base a {type(value_base).__name__} (one engine class)")
+    if getattr(pi_beta, "matmul", None) != getattr(value_base, "matmul", None):
+        raise _lib.LmrlError(f"value policy: pi_beta runs matmul = {pi_beta.matmul!r}, the value base {value_base.matmul!r} (one mode)")
+    if heads[0] is None:
+        raise _lib.LmrlError("value policy: q1_head is required")
+    for head in heads:
+        if head is not None:
+            pi_beta.check_value_head(head)
+
+
+def heads_to_engine_layout(head_params: dict, vocab_padded: int, device, engine=None) -> dict:
     """MLPHead params (`dense1.kernel` [d,d], `dense1.bias`, `dense2.kernel` [d,V], `dense2.bias`) -> bf16 [out][in] tensors
-    padded to `vocab_padded` rows for the fused sampler."""
+    padded to `vocab_padded` rows for the fused sampler.  engine: a `GPT2EngineF32` returns that engine's unrounded fp32 layout
+    (`GPT2EngineF32.value_head`) instead; None or a `GPT2Engine` keep the bf16 layout."""
     import torch
+    if engine is not None and hasattr(engine, "value_head"):
+        return engine.value_head(head_params)
     w1 = head_params["dense1.kernel"].t().contiguous().to(device, torch.bfloat16)
     V, d = head_params["dense2.kernel"].shape[1], head_params["dense2.kernel"].shape[0]
     w2 = torch.zeros(vocab_padded, d, dtype=torch.bfloat16, device=device)

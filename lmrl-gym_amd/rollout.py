@@ -156,9 +156,13 @@ class WordleRolloutEngine:
         """`session_flags`: lmrl_gpt2_forward variants (gpt2.FWD_*) of this engine's KV sessions (A/B hooks; results are bit-identical).
         `value_engine` + `q1_head` (+ `q2_head`) + `beta` turn the policy into the ILQL value policy
         (`GPT2ValueRLGeneration`, value_rl_base/gpt2/generation.py:97-119): `engine` is pi_beta, `value_engine` the value base
-        whose last hidden state feeds the Q heads (`policies.heads_to_engine_layout` dicts); logits = pi_beta + beta * min(Q1, Q2)."""
+        whose last hidden state feeds the Q heads (`policies.heads_to_engine_layout(..., engine=engine)` dicts); logits = pi_beta + beta * min(Q1, Q2)
+        (+ beta * Q1 without a q2_head: the MC-returns policy).  Both transformers are `GPT2Engine`s or both `GPT2EngineF32`s of one matmul mode."""
         import torch
         t = torch
+        if value_engine is not None:
+            from .policies import check_value_policy
+            check_value_policy(engine, value_engine, (q1_head, q2_head))
         self.eng, self.vocab, self.B = engine, vocab, batch
         self._twin_args = dict(tokens=tokens, max_new_tokens=max_new_tokens, require_words_in_vocab=require_words_in_vocab,
                                bad_word_reward=bad_word_reward, traj_cap=traj_cap, share_header=share_header, value_engine=value_engine,
@@ -187,7 +191,9 @@ class WordleRolloutEngine:
             self._aux_stream = _t.cuda.Stream(device=self.dev)
             self._ev_fork, self._ev_join = _t.cuda.Event(), _t.cuda.Event()
         self.vses1 = value_engine.session(1, 16) if value_engine is not None and share_header else None
-        self.qh = [t.zeros(batch, value_engine.cfg.d_model, dtype=t.bfloat16, device=self.dev) for _ in range(2)] if value_engine is not None else None
+        # the Q heads' dense1 outputs (and its split-K workspace on an fp32 value base): this engine's own, never shared with a lane twin
+        self.qh = [value_engine.q_hidden_buffer(batch) for _ in range(2)] if value_engine is not None else None
+        self._qh_ws = value_engine.q_hidden_ws(batch) if value_engine is not None else None
         ct = self.tokens.c_struct()
         cls = np.ascontiguousarray(self.tokens.token_class(engine.cfg.vocab))
         self._tok = self._L.lmrl_wordle_tok_create(ctypes.byref(ct), cls.ctypes.data, engine.cfg.vocab, max_new_tokens, traj_cap)
@@ -335,12 +341,10 @@ class WordleRolloutEngine:
                 self.sample_step += 1
                 qops = [None, None]
                 if self.vses is not None:     # Q heads on the value base's last hidden state: relu(dense1) here, dense2 inside the sampler
-                    dv = self.veng.cfg.d_model
                     for i, head in enumerate((self.q1, self.q2)):
                         if head is not None:
-                            self._ck(L.lmrl_gemm_bf16(_lib.ptr(self.vses.last_hidden), _lib.ptr(head["w1"]), _lib.ptr(head["b1"]), _lib.ptr(self.qh[i]),
-                                                      B, dv, dv, dv, dv, dv, 4, sp), "q head dense1 + relu")
-                            qops[i] = (self.qh[i], head["w2"], head["b2"])
+                            self.veng.q_hidden(head, self.vses.last_hidden, self.qh[i], self._qh_ws)
+                            qops[i] = (self.qh[i], head.get("w2_x3", head["w2"]), head["b2"])
                 self.ses.sample(p, steer_tok=steer, active=self.traj["gen_active"], logits_out=logits_out, q1=qops[0], q2=qops[1],
                                 want_logprob=False)
                 self._ck(L.lmrl_wordle_tok_accept(self._tok, tr, _lib.ptr(self.ses.token), k, _lib.ptr(self.next_tok),

@@ -78,10 +78,15 @@ def _model(spec: str, vocab: int):
     return cfg, {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
 
 
-def _engine(cfg, params):
+def _engine(cfg, params, kind: str = "bf16"):
+    """An inference engine over `params`: kind "bf16" = `GPT2Engine`; "f32" / "bf16x3" = `GPT2EngineF32` in that matmul mode."""
     from lmrl_gym_amd import _lib
     from lmrl_gym_amd.gpt2 import GPT2Engine
-    return GPT2Engine(cfg, {k: (v.detach().cpu() if hasattr(v, "detach") else v) for k, v in params.items()}, _lib.require_gpu())
+    sd = {k: (v.detach().cpu() if hasattr(v, "detach") else v) for k, v in params.items()}
+    if kind == "bf16":
+        return GPT2Engine(cfg, sd, _lib.require_gpu())
+    from lmrl_gym_amd.gpt2_f32_engine import GPT2EngineF32
+    return GPT2EngineF32(cfg, sd, _lib.require_gpu(), matmul=kind)
 
 
 def _wordle_env(a):
@@ -122,7 +127,7 @@ def cmd_ilql(a):
     cfg, sd = _model(a.model, max(len(tok), 50257))
     mm = dict(matmul="bf16" if a.bf16_activations else "f32")                 # the scripts' bf16_activations / gradient_checkpointing flags
     base = GPT2F32(sd, cfg.n_head, device=dev, gradient_checkpointing=a.gradient_checkpointing, **mm)
-    target_base, pi_beta = GPT2F32(sd, cfg.n_head, device=dev, **mm), _engine(cfg, sd)
+    target_base, pi_beta = GPT2F32(sd, cfg.n_head, device=dev, **mm), _engine(cfg, sd, a.policy_engine)
     d, V = cfg.d_model, cfg.vocab
     g = torch.Generator().manual_seed(0)
     # MLPHead init of train_ilql_gpt2.py:224-231: layer-2 kernel 0, layer-2 bias -4.4 (Q heads) ; V head likewise
@@ -136,18 +141,19 @@ def cmd_ilql(a):
     vocab, env = _wordle_env(a)
 
     def evaluate():
-        hl = lambda h: heads_to_engine_layout({k: v.detach().cpu() for k, v in h.p.items()}, cfg.vocab_padded, dev)
+        # --policy-engine f32 / bf16x3: the heads as the trainer holds them, unrounded (GPT2EngineF32.value_head)
+        hl = lambda h: heads_to_engine_layout({k: v.detach().cpu() for k, v in h.p.items()}, cfg.vocab_padded, dev, engine=pi_beta)
         if a.device_rollouts:       # ILQL value policy, env and loop on the GPU
             from lmrl_gym_amd.rollout import WordleRolloutEngine, WordleTokenTable
             table = getattr(tok, "table", None) or WordleTokenTable.from_tokenizer(tok)
             ro = WordleRolloutEngine(pi_beta, vocab, a.policy_bsize, tokens=table, max_new_tokens=min(a.policy_max_output_length, 12),
-                                     bad_word_reward=a.bad_word_reward, value_engine=_engine(cfg, base.p), q1_head=hl(tr.q1), q2_head=hl(tr.q2),
+                                     bad_word_reward=a.bad_word_reward, value_engine=_engine(cfg, base.p, a.policy_engine), q1_head=hl(tr.q1), q2_head=hl(tr.q2),
                                      beta=a.beta)
             _, summary = ro.text_env_eval(a.policy_n_rollouts, seed_generator=iter(range(10 ** 9)), temperature=a.policy_temperature or 1.0,
                                           top_k=int(a.policy_top_k or 0))
             ro.close()
             return summary
-        pol = GPT2ValuePolicy(pi_beta, _engine(cfg, base.p), hl(tr.q1), hl(tr.q2), a.beta, tok, max_input_length=a.policy_max_input_length,
+        pol = GPT2ValuePolicy(pi_beta, _engine(cfg, base.p, a.policy_engine), hl(tr.q1), hl(tr.q2), a.beta, tok, max_input_length=a.policy_max_input_length,
                               max_new_tokens=a.policy_max_output_length, do_sample=a.policy_do_sample, temperature=a.policy_temperature,
                               top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p, eos_token_id=tok.encode("\n")[0],
                               out_str_process=lambda x: x.removesuffix("\n") + "\n")
@@ -420,6 +426,9 @@ def build_parser() -> argparse.ArgumentParser:
         _add(p, defaults)
     sub.choices["ilql"].add_argument("--train-data", required=True)
     sub.choices["ilql"].add_argument("--eval-data", default=None)
+    sub.choices["ilql"].add_argument("--policy-engine", default="bf16", choices=["bf16", "f32", "bf16x3"],
+                                     help="evaluation engines of pi_beta and the value base: bf16 GPT2Engine (default) or GPT2EngineF32 in that matmul mode "
+                                          "(the reference evaluates in float32 by default) with unrounded heads")
     sub.choices["ppo"].add_argument("--bc-data", default=None)
     pp = sub.choices["ppo"]
     pp.add_argument("--env", default="wordle", choices=["wordle", "chess", "maze"])

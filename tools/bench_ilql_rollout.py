@@ -1,6 +1,10 @@
 """configs[2] rollouts: ILQL value policy (pi_beta + beta*min(Q1,Q2); two GPT-2-small transformers + two MLP Q heads 768->768->V)
-on the device-resident Wordle loop, 1024 envs, steered synthetic workload as in bench.py.  Prints env-steps/s."""
-import os, sys, time
+on the device-resident Wordle loop, 1024 envs, steered synthetic workload as in bench.py.  Prints env-steps/s.
+
+    python tools/bench_ilql_rollout.py [--engine bf16|f32|bf16x3] [plain]
+
+--engine: bf16 `GPT2Engine`s (default) or `GPT2EngineF32`s in that matmul mode with fp32 heads (the reference's default float32 evaluation)."""
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import lmrl_gym_amd  # noqa
@@ -12,13 +16,22 @@ from lmrl_gym_amd.rollout import WordleRolloutEngine
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import scripted_guesses
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--engine", default="bf16", choices=["bf16", "f32", "bf16x3"])
+ap.add_argument("legs", nargs="*")
+args = ap.parse_args()
 dev = _lib.require_gpu()
 cfg = GPT2Config.gpt2_small()
-pi_beta, base = GPT2Engine.random_init(cfg, seed=0, device=dev), GPT2Engine.random_init(cfg, seed=1, device=dev)
+if args.engine == "bf16":
+    pi_beta, base = GPT2Engine.random_init(cfg, seed=0, device=dev), GPT2Engine.random_init(cfg, seed=1, device=dev)
+else:
+    from lmrl_gym_amd.gpt2_f32_engine import GPT2EngineF32
+    pi_beta, base = (GPT2EngineF32.random_init(cfg, seed=s_, device=dev, matmul=args.engine) for s_ in (0, 1))
 g = torch.Generator().manual_seed(0)
 d, V = cfg.d_model, cfg.vocab
 mk = lambda: heads_to_engine_layout({"dense1.kernel": torch.randn(d, d, generator=g) * 0.02, "dense1.bias": torch.zeros(d),
-                                     "dense2.kernel": torch.randn(d, V, generator=g) * 0.002, "dense2.bias": torch.full((V,), -4.4)}, cfg.vocab_padded, dev)
+                                     "dense2.kernel": torch.randn(d, V, generator=g) * 0.002, "dense2.bias": torch.full((V,), -4.4)}, cfg.vocab_padded, dev,
+                                    engine=pi_beta)
 vocab = W.Vocabulary.builtin("wordle_official_400.txt")
 B, steps, warm = 1024, 4, 1
 ro = WordleRolloutEngine(pi_beta, vocab, B, max_new_tokens=6, bad_word_reward=-10.0, value_engine=base, q1_head=mk(), q2_head=mk(), beta=32.0)
@@ -33,8 +46,8 @@ torch.cuda.synchronize(); t0 = time.perf_counter()
 for i in range(warm, warm + steps):
     ro.replay_episode(seeds[i], guesses[i]); n += ro.traj["n_steps"].sum()
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
-print("ILQL value-policy rollouts: %.1f env-steps/s  (%.2f ms per 1024-env episode, %d env steps)" % (int(n) / dt, dt * 1e3 / steps, int(n)))
-if "plain" in sys.argv[1:]:          # profiling: the plain-sampling leg alone
+print("[%s] ILQL value-policy rollouts: %.1f env-steps/s  (%.2f ms per 1024-env episode, %d env steps)" % (args.engine, int(n) / dt, dt * 1e3 / steps, int(n)))
+if "plain" in args.legs:          # profiling: the plain-sampling leg alone
     sys.exit(0)
 
 # round 6: the task script's sampler — top-k on the perturbed logits (train_ilql_gpt2.py:384-403 `policy_top_k`, generation.py:97-119) — on the FUSED

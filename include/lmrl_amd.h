@@ -549,6 +549,31 @@ int lmrl_attn_cached_f32_split3(const float *qkv_d, float *kcache_d, float *vcac
                                 void *split3_out_d, int b, int c, int n_head, int tmax, void *stream);
 int lmrl_chunk_end_f32(const float *x_d, const int32_t *cnt_d, float *last_d, int32_t *len_d, int b, int c, int d, void *stream);
 
+/*
+ * fp32 prompt-prefix cache (csrc/kv_prefix_f32.hip, csrc/attn_cached_f32.hip): the fp32 twins of lmrl_gpt2_kv_gather / lmrl_gpt2_kv_attach /
+ * lmrl_gpt2_forward_prefixed for GPT2EngineF32 sessions (cache fp32 [n_layer][K|V][b][tmax][d]; last hidden and last residual fp32 [b][d]).
+ *   lmrl_kv_gather_f32   env i of dst starts from row idx_d[i] of the prefix session src: K/V positions [0, n) of every layer with
+ *                        n = min(src_len_d[row], dst_tmax, src_tmax), dst_len_d[i] = n and (optional) the row's last hidden state and last
+ *                        residual.  idx_d[i] < 0 (or >= src_b): empty cache.  All layers in one launch; dst rows >= n are not written.
+ *   lmrl_kv_attach_f32   the copy-free form: dst_len_d[i] = pfx_n_d[i] = n and the two last-state rows, nothing else; order_d (optional, [b]):
+ *                        the envs grouped by prefix row (the launch order of the prefixed attention).
+ *   lmrl_attn_decode_prefixed_f32  one layer's single-token decode attention (lmrl_attn_cached_f32_split3 with c = 1) for attached envs:
+ *                        positions [0, n_d[i]) of env i are READ from row row_d[i] of the prefix session's layer cache pfx_k_d / pfx_v_d
+ *                        ([pfx_rows][pfx_tmax][H*64]), positions [n_d[i], len_d[i]) from env i's own cache, and the new K / V row is
+ *                        appended to env i's own cache at len_d[i].  order_d (optional): launch order, each XCD walking a contiguous stretch
+ *                        of it.  Results are bit-identical to lmrl_attn_cached_f32_split3 after lmrl_kv_gather_f32 (same rows, same order
+ *                        of arithmetic), split3_out_d included.
+ */
+int lmrl_kv_gather_f32(const float *src_kv_d, int src_b, int src_tmax, const int32_t *src_len_d, const float *src_hidden_d, const float *src_last_x_d,
+                       const int32_t *idx_d, float *dst_kv_d, int dst_tmax, int b, float *dst_hidden_d, float *dst_last_x_d, int32_t *dst_len_d,
+                       int n_layer, int d, void *stream);
+int lmrl_kv_attach_f32(int src_b, int src_tmax, const int32_t *src_len_d, const float *src_hidden_d, const float *src_last_x_d, const int32_t *idx_d,
+                       int b, int dst_tmax, float *dst_hidden_d, float *dst_last_x_d, int32_t *dst_len_d, int32_t *pfx_n_d, int32_t *order_d, int d,
+                       void *stream);
+int lmrl_attn_decode_prefixed_f32(const float *qkv_d, float *kcache_d, float *vcache_d, const int32_t *len_d, const int32_t *cnt_d, float *out_d,
+                                  void *split3_out_d, int b, int n_head, int tmax, const float *pfx_k_d, const float *pfx_v_d, int pfx_rows,
+                                  int pfx_tmax, const int32_t *row_d, const int32_t *n_d, const int32_t *order_d, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * On-device token <-> game bookkeeping for lock-step Wordle rollouts (csrc/wordle_tokens.hip).
  * Replaces the per-turn host work of interact_environment + GPT2PPOPolicy.act

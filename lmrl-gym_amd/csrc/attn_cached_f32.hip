@@ -208,14 +208,33 @@ __global__ __launch_bounds__(256) void attn_chunk_f32_kernel(const float *__rest
 // per-position loop of the chunk kernel above pays one dependent memory latency per 4 positions.  Scores: 4 fmaf + a 16-lane DPP sum; softmax
 // per position slot g with ONE rescale per batch (U + 1 exps per U positions instead of 2 U), slots merged once at the end.  The new token's own
 // K / V row comes from `qkv`, is attended last by slot 0 and appended to the cache behind the load stream.  fp32 throughout, accurate expf.
-template <int U>
+//
+// PFX (indexed prompt prefix, lmrl_attn_decode_prefixed_f32; the fp32 form of gpt2.hip's DecodePrefix): positions [0, pn) of env b, pn = pfx.n[b],
+// are the rows of row pfx.row[b] of ANOTHER session's layer cache (the prompt-prefix cache, one prefill per distinct prompt) and are read from
+// there; positions [pn, len[b]) come from the env's own cache at their absolute positions, as without a prefix.  A 4-position block that
+// straddles pn picks its source per lane (one select of the row address): the load batch, the positions it covers and the order of arithmetic
+// are those of the copying form, so the results are bit-identical to it.  Plain loads (not streaming): rows shared by several envs are meant to
+// be served from L2.  pfx.order (optional) lists the envs grouped by prefix row, and workgroup ids are spread so that each XCD walks a
+// contiguous stretch of that list (the waves resident on one XCD share a handful of prompts, whose rows then stay in that XCD's L2).
+struct DecodePrefixF32 {
+    const float *k, *v;          // this layer's K / V block of the prefix session: [n_rows][tmax][d]
+    const int32_t *row, *n, *order;
+    int n_rows, tmax;
+};
+
+template <int U, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_decode_f32_kernel(const float *__restrict__ qkv, float *__restrict__ kcache, float *__restrict__ vcache,
                                                               const int32_t *__restrict__ len, const int32_t *__restrict__ cnt,
-                                                              float *__restrict__ out, int B, int H, int tmax, uint16_t *__restrict__ split) {
+                                                              float *__restrict__ out, int B, int H, int tmax, uint16_t *__restrict__ split,
+                                                              DecodePrefixF32 pfx) {
     const int lane = threadIdx.x & 63;
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);                 // wave id = b * H + h
+    int w = blockIdx.x * 4 + (threadIdx.x >> 6);                       // wave id = b * H + h
+    if (PFX && pfx.order && (gridDim.x & 7) == 0)                      // workgroup ids round-robin over the 8 XCDs: XCD x gets ids [x, x + 8, ..]
+        w = ((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) * 4 + (threadIdx.x >> 6);
     if (w >= B * H) return;
-    const int b = w / H, h = w - b * H;
+    int b = w / H;
+    const int h = w - b * H;
+    if (PFX && pfx.order) b = pfx.order[b];
     const int g = lane >> 4, c = lane & 15;
     const int d = H * kDh;
     const float *row = qkv + (size_t)b * 3 * d + h * kDh + c * 4;
@@ -229,6 +248,17 @@ __global__ __launch_bounds__(256) void attn_decode_f32_kernel(const float *__res
     q4.x *= 0.125f; q4.y *= 0.125f; q4.z *= 0.125f; q4.w *= 0.125f;    // 1 / sqrt(64): a power of two, exact
     const float *kc = kcache + (size_t)b * tmax * d + h * kDh + c * 4;
     const float *vc = vcache + (size_t)b * tmax * d + h * kDh + c * 4;
+    // PFX: positions < pn come from row r of the prefix session (wave-uniform scalars; the per-lane choice is one select per operand)
+    int pn = 0;
+    const float *pkc = kc, *pvc = vc;
+    if constexpr (PFX) {
+        const int r = pfx.row[b];
+        if (r >= 0 && r < pfx.n_rows) {
+            pn = min(pfx.n[b], pfx.tmax);
+            pkc = pfx.k + (size_t)r * pfx.tmax * d + h * kDh + c * 4;
+            pvc = pfx.v + (size_t)r * pfx.tmax * d + h * kDh + c * 4;
+        }
+    }
     float m = -1e30f, l = 0.f;
     float4 o = {0.f, 0.f, 0.f, 0.f};
     for (int t0 = 0; t0 < L; t0 += 4 * U) {
@@ -237,11 +267,18 @@ __global__ __launch_bounds__(256) void attn_decode_f32_kernel(const float *__res
         for (int u = 0; u < U; u++)
             if (t0 + u * 4 < L) {                                      // wave-uniform: block u holds cached positions
                 const int t = t0 + u * 4 + g;
-                const size_t ro = (size_t)(t < L ? t : L - 1) * d;
-                // (streaming loads: every cached row is read by ONE wave per decode step — as in the bf16 engine's decode attention, csrc/gpt2.hip)
-                typedef float f32x4_nt __attribute__((ext_vector_type(4)));
-                kr[u] = __builtin_bit_cast(float4, __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt *>(kc + ro)));
-                vr[u] = __builtin_bit_cast(float4, __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt *>(vc + ro)));
+                const int tc = t < L ? t : L - 1;
+                const size_t ro = (size_t)tc * d;
+                if constexpr (PFX) {
+                    const bool in_p = tc < pn;
+                    kr[u] = *reinterpret_cast<const float4 *>((in_p ? pkc : kc) + ro);
+                    vr[u] = *reinterpret_cast<const float4 *>((in_p ? pvc : vc) + ro);
+                } else {
+                    // (streaming loads: every cached row is read by ONE wave per decode step — as in the bf16 engine's decode attention, csrc/gpt2.hip)
+                    typedef float f32x4_nt __attribute__((ext_vector_type(4)));
+                    kr[u] = __builtin_bit_cast(float4, __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt *>(kc + ro)));
+                    vr[u] = __builtin_bit_cast(float4, __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt *>(vc + ro)));
+                }
             }
         float sc[U];
         float mb = m;
@@ -341,7 +378,7 @@ int lmrl_attn_cached_f32_split3(const float *qkv_d, float *kcache_d, float *vcac
     const long waves = (long)b * c * n_head;
     if (c == 1)      // single-token decode: the batched-load kernel (32 cached positions requested per wave before any arithmetic)
         hipLaunchKernelGGL(attn_decode_f32_kernel<8>, dim3(ceil_div(waves, 4)), dim3(256), 0, as_stream(stream), qkv_d, kcache_d, vcache_d, len_d, cnt_d,
-                           out_d, b, n_head, tmax, (uint16_t *)split3_out_d);
+                           out_d, b, n_head, tmax, (uint16_t *)split3_out_d, DecodePrefixF32{});
     else if (c == 8)      // the per-turn chunk: one wave per (env, head) scores every K / V row against all 8 queries
         hipLaunchKernelGGL(attn_chunk_f32_kernel<8>, dim3(ceil_div((long)b * n_head, 4)), dim3(256), 0, as_stream(stream), qkv_d, kcache_d, vcache_d, len_d,
                            cnt_d, out_d, b, n_head, tmax, (uint16_t *)split3_out_d);
@@ -351,6 +388,19 @@ int lmrl_attn_cached_f32_split3(const float *qkv_d, float *kcache_d, float *vcac
     else
         hipLaunchKernelGGL(attn_cached_f32_kernel, dim3(ceil_div(waves, 4)), dim3(256), 0, as_stream(stream), qkv_d, kcache_d, vcache_d, len_d, cnt_d,
                            out_d, b, c, n_head, tmax, (uint16_t *)split3_out_d);
+    LMRL_CHECK_LAUNCH();
+    return LMRL_OK;
+}
+
+int lmrl_attn_decode_prefixed_f32(const float *qkv_d, float *kcache_d, float *vcache_d, const int32_t *len_d, const int32_t *cnt_d, float *out_d,
+                                  void *split3_out_d, int b, int n_head, int tmax, const float *pfx_k_d, const float *pfx_v_d, int pfx_rows,
+                                  int pfx_tmax, const int32_t *row_d, const int32_t *n_d, const int32_t *order_d, void *stream) {
+    LMRL_REQUIRE(qkv_d && kcache_d && vcache_d && len_d && cnt_d && out_d && b > 0 && n_head > 0 && tmax > 0,
+                 "lmrl_attn_decode_prefixed_f32: bad argument");
+    LMRL_REQUIRE(pfx_k_d && pfx_v_d && row_d && n_d && pfx_rows > 0 && pfx_tmax > 0, "lmrl_attn_decode_prefixed_f32: bad prefix");
+    const DecodePrefixF32 pfx{pfx_k_d, pfx_v_d, row_d, n_d, order_d, pfx_rows, pfx_tmax};
+    hipLaunchKernelGGL((attn_decode_f32_kernel<8, true>), dim3(ceil_div((long)b * n_head, 4)), dim3(256), 0, as_stream(stream), qkv_d, kcache_d, vcache_d,
+                       len_d, cnt_d, out_d, b, n_head, tmax, (uint16_t *)split3_out_d, pfx);
     LMRL_CHECK_LAUNCH();
     return LMRL_OK;
 }

@@ -93,7 +93,7 @@ int lmrl_prof_read(int tag, double *total_ms, double *total_work, long long *lau
 
 const char *lmrl_last_error(void) { return lmrl::g_err; }
 
-int lmrl_version(void) { return 102; }
+int lmrl_version(void) { return 103; }
 
 const char *lmrl_device_arch(void) {
     static char arch[256] = "";

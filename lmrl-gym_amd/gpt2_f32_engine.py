@@ -17,6 +17,10 @@ parameters out unrounded, `q_hidden` computes relu(dense1) in exact fp32 on the 
 takes the dense2 products: in "f32" mode one launch of `lmrl_value_head_logits_f32` (the three products and the combine on the f32 MFMA, csrc/
 value_head_f32.hip) into the materialised logits, then the same sampler; in "bf16x3" mode the fused LM-head sampler with three split operands at
 K' = 3 d.
+
+The prompt-prefix cache of the Maze device loop works here as on the bf16 engine: `KVSessionF32.gather_prefix_from` copies prompt rows of a prefix
+session into every env's cache (`lmrl_kv_gather_f32`), `attach_prefix_from` only points the envs at them (`lmrl_kv_attach_f32`), and the decode
+forwards of an attached session read the prompt positions from the prefix rows (`lmrl_attn_decode_prefixed_f32`, bit-identical to the copy).
 """
 from __future__ import annotations
 
@@ -180,6 +184,8 @@ class KVSessionF32:
             self._q_split = [t.empty(batch * 3 * c.d_model, dtype=t.bfloat16, device=dev) for _ in range(2)]
         self._ws = {}
         self._len_bound = 0
+        self._prefix = None     # (src, idx, pfx_n, order or None) while the envs stand on rows of a prompt-prefix session (attach_prefix_from)
+        self._pfx_n = self._pfx_order = None
 
     def _bufs(self, C):
         import torch
@@ -201,12 +207,16 @@ class KVSessionF32:
     def reset(self):
         self.len.zero_()
         self._len_bound = 0
+        self._prefix = None
 
     def forward(self, tokens, cnt, chunk: int, all_hidden=None, len_bound_after: Optional[int] = None):
         """tokens int32 [B*chunk], cnt int32 [B] (env b's new tokens are slots b*chunk .. b*chunk + cnt[b] - 1): appends them to the cache,
         advances self.len, leaves ln_f(hidden of each env's last new token) in self.last_hidden."""
         e, c, L, sp = self.eng, self.eng.cfg, self.eng._L, _lib.stream_ptr()
         C, B, d, R = chunk, self.B, c.d_model, self.B * chunk
+        pfx = self._prefix
+        if pfx is not None and (C != 1 or all_hidden is not None):
+            raise _lib.LmrlError("a session attached to a prompt-prefix cache takes single-token decode forwards only (reset() it first)")
         self._len_bound = self._len_bound + C if len_bound_after is None else int(len_bound_after)
         if self._len_bound > self.tmax:
             raise _lib.LmrlError(f"KV cache overflow: up to {self._len_bound} positions into a cache of tmax = {self.tmax}")
@@ -229,8 +239,15 @@ class KVSessionF32:
         for l, p in enumerate(e.layers):
             e.linear(ln(pending, p["ln_1.weight"], p["ln_1.bias"]), R, d, 3 * d, "attn.c_attn", p, qkv, w["split"], splitk_ws=sk)
             # (bf16x3: the attention lanes that hold the output also write it as the projection GEMM's split operand — no split pass)
-            _lib.check(L.lmrl_attn_cached_f32_split3(_lib.ptr(qkv), _lib.ptr(self.kv[l, 0]), _lib.ptr(self.kv[l, 1]), _lib.ptr(self.len), _lib.ptr(cnt),
-                                                     _lib.ptr(att), _lib.ptr(w["split"]) if x3 else None, B, C, c.n_head, self.tmax, sp), "lmrl_attn_cached_f32")
+            if pfx is not None:        # attached: the prompt positions are read from the prefix session's rows of this layer
+                src, idx, pn, order = pfx
+                _lib.check(L.lmrl_attn_decode_prefixed_f32(_lib.ptr(qkv), _lib.ptr(self.kv[l, 0]), _lib.ptr(self.kv[l, 1]), _lib.ptr(self.len), _lib.ptr(cnt),
+                                                           _lib.ptr(att), _lib.ptr(w["split"]) if x3 else None, B, c.n_head, self.tmax, _lib.ptr(src.kv[l, 0]),
+                                                           _lib.ptr(src.kv[l, 1]), src.B, src.tmax, _lib.ptr(idx), _lib.ptr(pn), _lib.ptr(order), sp),
+                           "lmrl_attn_decode_prefixed_f32")
+            else:
+                _lib.check(L.lmrl_attn_cached_f32_split3(_lib.ptr(qkv), _lib.ptr(self.kv[l, 0]), _lib.ptr(self.kv[l, 1]), _lib.ptr(self.len), _lib.ptr(cnt),
+                                                         _lib.ptr(att), _lib.ptr(w["split"]) if x3 else None, B, C, c.n_head, self.tmax, sp), "lmrl_attn_cached_f32")
             e.linear(None if x3 else att, R, d, d, "attn.c_proj", p, r, w["split"], splitk_ws=sk)   # r = att . Wproj + b ; x += r inside the ln_2 launch
             if x3:
                 # c_fc reads the LayerNorm's split operand (w["split"], pitch 3 d) and writes gelu's split operand (w["split2"], pitch 3 d_ff)
@@ -257,6 +274,7 @@ class KVSessionF32:
         assert lens.shape == (self.B,) and int(lens.max(initial=0)) <= self.tmax
         self.len.copy_(torch.from_numpy(lens))
         self._len_bound = int(lens.max(initial=0))
+        self._prefix = None
 
     def broadcast_prefix_from(self, src: "KVSessionF32", n_pos: int):
         """Every env starts with the n_pos-token prefix held by the 1-env session `src` (device-to-device row copies)."""
@@ -266,6 +284,40 @@ class KVSessionF32:
         self.last_hidden.copy_(src.last_hidden.expand(self.B, -1))
         self.len.fill_(n_pos)
         self._len_bound = max(self._len_bound, n_pos)
+        self._prefix = None
+
+    def gather_prefix_from(self, src: "KVSessionF32", idx, max_pos: int):
+        """Env b starts from the prompt held by row idx[b] (int32 device tensor; < 0: empty cache) of the session `src` of the same engine
+        (`lmrl_kv_gather_f32`, one launch): K/V rows of every layer, cache length, last hidden state and last residual.  `max_pos` bounds the
+        copied prompt lengths."""
+        assert src.eng is self.eng
+        c = self.eng.cfg
+        if max_pos > self.tmax:
+            raise _lib.LmrlError(f"KV cache overflow: prompts of up to {max_pos} positions into a cache of tmax = {self.tmax}")
+        _lib.check(self.eng._L.lmrl_kv_gather_f32(_lib.ptr(src.kv), src.B, src.tmax, _lib.ptr(src.len), _lib.ptr(src.last_hidden), _lib.ptr(src._last_x),
+                                                  _lib.ptr(idx), _lib.ptr(self.kv), self.tmax, self.B, _lib.ptr(self.last_hidden), _lib.ptr(self._last_x),
+                                                  _lib.ptr(self.len), c.n_layer, c.d_model, _lib.stream_ptr()), "lmrl_kv_gather_f32")
+        self._len_bound = max_pos
+        self._prefix = None
+
+    def attach_prefix_from(self, src: "KVSessionF32", idx, max_pos: int, group: bool = True):
+        """The copy-free form of `gather_prefix_from` (`lmrl_kv_attach_f32` + `lmrl_attn_decode_prefixed_f32`): env b's positions below the prompt
+        length of row idx[b] are READ from `src`'s cache by the decode attention; only the generated tokens' rows are written to this session.  `idx`
+        must stay alive and unchanged until the next attach / reset (it is the kernel's row table); `group`: launch the envs grouped by prefix row
+        (rows shared by several envs are then served from L2).  Decode forwards only (a chunk forward raises `LmrlError`)."""
+        import torch
+        assert src.eng is self.eng
+        e = self.eng
+        if max_pos > self.tmax:
+            raise _lib.LmrlError(f"KV cache overflow: prompts of up to {max_pos} positions into a cache of tmax = {self.tmax}")
+        if self._pfx_n is None:
+            self._pfx_n = torch.zeros(self.B, dtype=torch.int32, device=e.device)
+            self._pfx_order = torch.zeros(self.B, dtype=torch.int32, device=e.device)
+        _lib.check(e._L.lmrl_kv_attach_f32(src.B, src.tmax, _lib.ptr(src.len), _lib.ptr(src.last_hidden), _lib.ptr(src._last_x), _lib.ptr(idx), self.B,
+                                           self.tmax, _lib.ptr(self.last_hidden), _lib.ptr(self._last_x), _lib.ptr(self.len), _lib.ptr(self._pfx_n),
+                                           _lib.ptr(self._pfx_order) if group else None, e.cfg.d_model, _lib.stream_ptr()), "lmrl_kv_attach_f32")
+        self._prefix = (src, idx, self._pfx_n, self._pfx_order if group else None)
+        self._len_bound = max_pos
 
     def lm_logits(self, hidden=None):
         """logits fp32 [B][vocab_padded] = hidden . wte^T (tied LM head) into self.logits."""

@@ -8,7 +8,9 @@ With last_k = 1 the policy's prompt is the observation of the current cell — a
 them ONCE per set of weights into a prompt-prefix cache (one KV row per observation).  By default the envs then only POINT at their row
 (`lmrl_gpt2_kv_attach`): the decode attention reads the prompt positions from the cache row itself (`lmrl_gpt2_forward_prefixed`), envs
 standing on the same cell share those bytes through L2, and only the generated tokens' rows are written per env;
-`prefix_indexed=False` copies the rows per env per turn instead (`lmrl_gpt2_kv_gather`, bit-identical).  A turn is then
+`prefix_indexed=False` copies the rows per env per turn instead (`lmrl_gpt2_kv_gather`, bit-identical).  On the fp32 rollout engine
+(`GPT2EngineF32`, both matmul modes: the Maze scripts' default float32 arithmetic) the same calls are `lmrl_kv_attach_f32` /
+`lmrl_attn_decode_prefixed_f32` and `lmrl_kv_gather_f32`.  A turn is then
 
     obs row <- env state | K/V + last hidden <- prefix cache | generate <= max_new ids | ids -> action code | lmrl_maze_step | record
 
@@ -85,7 +87,12 @@ class MazeRolloutEngine:
     `value_engine` + `q1_head` (+ `q2_head`) + `beta` make it the ILQL value policy (value_rl_base/gpt2/generation.py:97-119), as in
     `WordleRolloutEngine`.  `prefix_cache=False` prefills the observation tokens per env per turn instead (16-token chunks): the
     cross-check of the cache, and the fallback for tables too large to prefill; `prefix_indexed=False` keeps the cache but copies its rows
-    into every env's own cache each turn (the cross-check of the indexed attention)."""
+    into every env's own cache each turn (the cross-check of the indexed attention).
+
+    `engine` (and `value_engine`) may be `GPT2Engine`s (bf16) or `GPT2EngineF32`s (the reference's default float32; both matmul modes): every
+    feature above runs on either, pi_beta and the value base being engines of one class and mode (`policies.check_value_policy`).  The skinny-M
+    products of B <= 16 envs (`FWD_SKINNY`) exist for the bf16 engine only: fp32 sessions are not given the flag.  `load_params` (in-place weights)
+    is bf16-only too: an fp32 policy takes new weights through `set_params`."""
 
     def __init__(self, engine: GPT2Engine, tokenizer, env: M.MazeEnv, batch: int, max_new_tokens: int = 8, eos_token_id: Optional[int] = None,
                  max_input_length: int = 256, in_str_process: Optional[Callable[[str], str]] = None, prefix_cache: bool = True,
@@ -94,6 +101,9 @@ class MazeRolloutEngine:
                  q2_head: Optional[dict] = None, beta: float = 0.0, session_flags: int = FWD_RAGGED_ALWAYS):
         import torch
         t = torch
+        if value_engine is not None:
+            from .policies import check_value_policy
+            check_value_policy(engine, value_engine, (q1_head, q2_head))
         # text_env_eval(concurrent=n): a twin engine needs its own vectorised env (device state) — possible when the caller handed over a MazeEnv
         self._twin_args = dict(tokenizer=tokenizer, env=env if isinstance(env, M.MazeEnv) else None, batch=batch, max_new_tokens=max_new_tokens,
                                eos_token_id=eos_token_id, max_input_length=max_input_length, in_str_process=in_str_process, prefix_cache=prefix_cache,
@@ -155,12 +165,14 @@ class MazeRolloutEngine:
         self.veng, self.q1, self.q2, self.beta = value_engine, q1_head, q2_head, float(beta)
         assert (value_engine is None) == (q1_head is None), "value_engine and q1_head come together"
         self.engines = [engine] + ([value_engine] if value_engine is not None else [])
-        if batch <= 16:
+        if batch <= 16 and isinstance(engine, GPT2Engine):
             session_flags |= FWD_SKINNY             # a handful of envs (configs[0]: 8): decode products on the skinny-M kernels (csrc/skinny_gemm.h)
         self.sessions = [e.session(batch, tmax, flags=session_flags) for e in self.engines]
         self.ses = self.sessions[0]
         self.vses = self.sessions[1] if value_engine is not None else None
-        self.qh = [t.zeros(batch, value_engine.cfg.d_model, dtype=t.bfloat16, device=self.dev) for _ in range(2)] if value_engine is not None else None
+        # the Q heads' dense1 outputs (and their split-K workspace on an fp32 value base): this engine's own, never shared with a lane twin
+        self.qh = [value_engine.q_hidden_buffer(batch) for _ in range(2)] if value_engine is not None else None
+        self._qh_ws = value_engine.q_hidden_ws(batch) if value_engine is not None else None
         self.caches = None
         B, G, T = batch, max_new_tokens, self.T
         z = lambda *shape, dt: t.zeros(*shape, dtype=dt, device=self.dev)
@@ -272,7 +284,11 @@ class MazeRolloutEngine:
 
     def load_params(self, params) -> None:
         """The trainer's fp32 parameters into the policy engine IN PLACE (`GPT2Engine.load_params`: captured turns stay valid, they read the same
-        weight buffers), then the observation prefix cache again — its K/V rows were computed by the old weights."""
+        weight buffers), then the observation prefix cache again — its K/V rows were computed by the old weights.  bf16 policy engines only: a
+        `GPT2EngineF32` policy is rebuilt from the trained weights and handed to `set_params`."""
+        if not isinstance(self.eng, GPT2Engine):
+            raise _lib.LmrlError(f"MazeRolloutEngine.load_params: in-place loading needs a bf16 GPT2Engine policy, not a {type(self.eng).__name__} "
+                                 "(build an engine from the new weights and call set_params)")
         self.eng.load_params(params)
         self._drop_lanes()
         if self.prefix_cache:
@@ -320,13 +336,11 @@ class MazeRolloutEngine:
         for k in range(self.max_new):
             p = SampleParams(temperature, top_k, sample_seed, k, script[3] if script is not None else 0.0, self.beta, self.pad, _lib.ptr(self.epoch))
             qops = [None, None]
-            if self.vses is not None:
-                dv = self.veng.cfg.d_model
+            if self.vses is not None:     # Q heads on the value base's last hidden state: relu(dense1) here, dense2 inside the sampler
                 for i, head in enumerate((self.q1, self.q2)):
                     if head is not None:
-                        ck(L.lmrl_gemm_bf16(_lib.ptr(self.vses.last_hidden), _lib.ptr(head["w1"]), _lib.ptr(head["b1"]), _lib.ptr(self.qh[i]),
-                                            B, dv, dv, dv, dv, dv, 4, sp), "q head dense1 + relu")
-                        qops[i] = (self.qh[i], head["w2"], head["b2"])
+                        self.veng.q_hidden(head, self.vses.last_hidden, self.qh[i], self._qh_ws)
+                        qops[i] = (self.qh[i], head.get("w2_x3", head["w2"]), head["b2"])
             self.ses.sample(p, steer_tok=script[2][k] if script is not None else None, active=self.traj["gen_active"], logits_out=logits_out, q1=qops[0],
                             q2=qops[1], want_logprob=False)
             ck(L.lmrl_gen_accept(_lib.ptr(self.ses.token), _lib.ptr(self.traj["gen_active"]), _lib.ptr(self.traj["out_tok"]),

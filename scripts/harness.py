@@ -396,7 +396,7 @@ def cmd_maze_eval(a):
     from lmrl_gym_amd.policies import GPT2PPOPolicy
     tok = _tokenizer(wordle=False)
     cfg, sd = _model(a.model, max(len(tok), 50257))
-    policy = GPT2PPOPolicy(_engine(cfg, sd), tok, max_input_length=a.max_input_length, max_new_tokens=a.max_output_length, do_sample=False,
+    policy = GPT2PPOPolicy(_engine(cfg, sd, a.policy_engine), tok, max_input_length=a.max_input_length, max_new_tokens=a.max_output_length, do_sample=False,
                            eos_token_id=tok.encode("\n")[0], out_str_process=lambda x: x.removesuffix("\n") + "\n")
     env = M.setup_maze_env(a.maze_name, a.describe_function, a.reward_function, last_k=a.last_k, max_steps=a.max_steps)
     starts = [tuple(p) for p in np.argwhere(M.double_t_maze() == 0).tolist()]        # one rollout per free cell (fully_observed_bc.py:262-283)
@@ -429,6 +429,9 @@ def build_parser() -> argparse.ArgumentParser:
     sub.choices["ilql"].add_argument("--policy-engine", default="bf16", choices=["bf16", "f32", "bf16x3"],
                                      help="evaluation engines of pi_beta and the value base: bf16 GPT2Engine (default) or GPT2EngineF32 in that matmul mode "
                                           "(the reference evaluates in float32 by default) with unrounded heads")
+    sub.choices["maze-eval"].add_argument("--policy-engine", default="bf16", choices=["bf16", "f32", "bf16x3"],
+                                          help="evaluation engine of the policy: bf16 GPT2Engine (default) or GPT2EngineF32 in that matmul mode "
+                                               "(the reference's Maze scripts evaluate in float32 by default)")
     sub.choices["ppo"].add_argument("--bc-data", default=None)
     pp = sub.choices["ppo"]
     pp.add_argument("--env", default="wordle", choices=["wordle", "chess", "maze"])

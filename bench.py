@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py — headline metric of BASELINE.json: env-steps/sec, GPT-2-small Wordle rollouts, 1024 envs per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the result line.  `--full`
+adds everything else the line has carried (roofline and per-kernel figures, text_env_eval, the fp32 / bf16x3 engines, the train step, the
+RL-reduction kernels, sampling warpers, Maze, the PPO iteration, larger batches, the CPU baseline and the env kernel alone); the timed
+steps and their inputs are the same in both.
 
 One "step" = one lock-step EPISODE of the hot path over one batch: 1024 envs x up to 6 turns, each turn =
 GPT-2-small policy samples an action token by token (persistent KV cache, fused LM-head sampler), the batched
@@ -796,6 +801,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=1024, help="envs per GPU")
     ap.add_argument("--vocab-file", default="wordle_official_400.txt")
+    ap.add_argument("--full", action="store_true", help="rollout mode: after the headline, run every other leg of the line (roofline and per-kernel "
+                    "figures, text_env_eval, fp32 / bf16x3 engines, train step, RL reductions, warpers, Maze, PPO iteration, larger batches, CPU "
+                    "baseline, env kernel alone); the --no-* options below skip single legs of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", type=int, default=1, help="1: capture the episode into a hipGraph and replay it (default); 0: eager launches")
     ap.add_argument("--share-header", type=int, default=1, help="1 (default): the K/V rows of the header text every env starts from are computed "
@@ -804,17 +812,17 @@ def main():
     ap.add_argument("--session-flags", type=int, default=0, help="lmrl_gpt2_forward variant bits of the headline engine's KV sessions (A/B runs: 64 / 128 = decode "
                                                                  "attention with 2 / 3 (env, head) items per wave)")
     ap.add_argument("--breakdown", action="store_true", help="after the timed region, print a per-kernel-class event breakdown to stderr")
-    ap.add_argument("--no-fp32-mode", action="store_true", help="skip the `fp32_mode` leg of the default line (the same rollout on the fp32 engine)")
-    ap.add_argument("--no-batch-sweep", action="store_true", help="skip the informational `larger_batches` leg of the default line (the same run at 4096 and 8192 envs per GPU, child processes)")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the `train_step` leg of the default line (ILQL M3 step, fp32 and bf16-matmul)")
-    ap.add_argument("--no-rl-reduce", action="store_true", help="skip the `rl_reduce` leg of the default line (GAE / reward-to-go / whitening kernels at 4096 and 65536 chains)")
+    ap.add_argument("--no-fp32-mode", action="store_true", help="skip the `fp32_mode` leg of the --full line (the same rollout on the fp32 engine)")
+    ap.add_argument("--no-batch-sweep", action="store_true", help="skip the informational `larger_batches` leg of the --full line (the same run at 4096 and 8192 envs per GPU, child processes)")
+    ap.add_argument("--no-train-step", action="store_true", help="skip the `train_step` leg of the --full line (ILQL M3 step, fp32 and bf16-matmul)")
+    ap.add_argument("--no-rl-reduce", action="store_true", help="skip the `rl_reduce` leg of the --full line (GAE / reward-to-go / whitening kernels at 4096 and 65536 chains)")
     ap.add_argument("--mode-rl-reduce-only", action="store_true", help="run ONLY the `rl_reduce` leg and print it as a JSON line (profiling: tools/prof_rl_reduce.sh)")
-    ap.add_argument("--no-maze", action="store_true", help="skip the `maze_rollout` and `sampling_warpers` legs of the default line (configs[0]'s Maze env on the device loop at 8 and 1024 envs; the headline workload with top-k / top-p)")
-    ap.add_argument("--no-ppo-iteration", action="store_true", help="skip the `ppo_iteration` leg of the default line (rollouts -> PPO data -> 4 train steps -> weights pushed back, device-resident and host path)")
+    ap.add_argument("--no-maze", action="store_true", help="skip the `maze_rollout` and `sampling_warpers` legs of the --full line (configs[0]'s Maze env on the device loop at 8 and 1024 envs; the headline workload with top-k / top-p)")
+    ap.add_argument("--no-ppo-iteration", action="store_true", help="skip the `ppo_iteration` leg of the --full line (rollouts -> PPO data -> 4 train steps -> weights pushed back, device-resident and host path)")
     ap.add_argument("--ppo-iters", type=int, default=2, help="`ppo_iteration` leg: timed iterations per arithmetic mode (after one warm-up iteration)")
     ap.add_argument("--ppo-train-steps", type=int, default=4, help="`ppo_iteration` leg: gradient steps per iteration (32 sequences each)")
     ap.add_argument("--ppo-max-length", type=int, default=1024, help="`ppo_iteration` leg: blocking width of the PPO data / train batches (the script's 512 + 512)")
-    ap.add_argument("--train-steps", type=int, default=5, help="timed steps per arithmetic mode in the `train_step` leg of the default line")
+    ap.add_argument("--train-steps", type=int, default=5, help="timed steps per arithmetic mode in the `train_step` leg of the --full line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the episode records of the last timed step (the `traj` arrays a caller of replay_episode / "
                          "run_episode receives, rank 0's envs) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array by array")
@@ -863,7 +871,8 @@ def main():
             ros.append(WordleRolloutEngine(eng, vocab, Bs, max_new_tokens=6, bad_word_reward=-10.0, share_header=bool(args.share_header),
                                            session_flags=args.session_flags))
     ro = ros[0]
-    n_eps = max(args.steps, 2) + args.warmup + (1 if args.breakdown else 0)      # (the roofline leg replays episodes warmup .. warmup + 1 eagerly)
+    # (the --full roofline leg replays episodes warmup .. warmup + 1 eagerly; a plain run draws the same count, so its guesses are the same)
+    n_eps = max(args.steps, 2) + args.warmup + (1 if args.breakdown else 0)
     guesses = torch.from_numpy(scripted_guesses(vocab.all_vocab, n_eps, n_turns, B, seed=12345 + rank).view(np.int32)).to(dev)
     guesses_s = [guesses[:, :, k * Bs:(k + 1) * Bs].contiguous() for k in range(S)]
     # env seeds of every episode resident in HBM up front: no host->device copy (= host sync) between episodes
@@ -936,125 +945,6 @@ def main():
     if args.dump_outputs and rank == 0:
         # the last timed step's records, before the legs below reuse the engines' buffers
         dump_outputs(args.dump_outputs, {n: torch.cat([r.traj[n] for r in ros]) for n in ro.traj})
-    # what a drop-in caller of `text_env_eval` pays on top of the device episode (LLM_RL/environment.py:211-267 returns HOST lists of
-    # InteractionTransition): device -> host copy of the records + building the Python objects for this rank's B envs.  Outside `value`.
-    th = time.perf_counter()
-    n_trans = sum(len(ep) for r in ros for ep in r.interactions())
-    host_materialise_ms = (time.perf_counter() - th) * 1e3
-    # ... and the public call itself on the same steered workload: `WordleRolloutEngine.text_env_eval` over 4 episode batches (graph
-    # replays; the host builds batch k's transition lists while the device runs batch k + 1), env steps returned / wall time
-    tev = None
-    if S == 1:
-        n_b = min(4, n_eps)
-        gen_seeds = iter(range(10 ** 6, 10 ** 9))
-        kwf = dict(scripted_guesses_fn=lambda bid: guesses[bid % n_eps], steer_strength=30.0, temperature=1.0, sample_seed=9, use_graph=True)
-        ro.text_env_eval(B, seed_generator=gen_seeds, **kwf)       # warm: pinned buffers, graph capture
-        torch.cuda.synchronize(); th = time.perf_counter()
-        inter_all, _summary = ro.text_env_eval(n_b * B, seed_generator=gen_seeds, **kwf)
-        tev_s = time.perf_counter() - th
-        tev = dict(value=round(sum(len(ep) for ep in inter_all) / tev_s, 1), unit="env-steps/s", episode_batches=n_b, ms_per_batch=round(tev_s * 1e3 / n_b, 2),
-                   note="rank 0: WordleRolloutEngine.text_env_eval(n_rollouts = 4 x B) end to end — device episodes (hipGraph replays) + host lists of "
-                        "InteractionTransition + summary dict, host materialisation of batch k overlapped with the device work of batch k + 1")
-        del inter_all
-        # three episode batches in flight (concurrent=3: twin engines — own KV cache, env state, graph — on their own HIP streams over the same
-        # weights): each batch is still one lock-step batch of B envs; the dependent launch chains fill each other's gaps on the 256 CUs
-        n_b2 = 12
-        ro.text_env_eval(3 * B, seed_generator=gen_seeds, concurrent=3, **kwf)      # warm: twin engines, their graphs, pinned buffers
-        torch.cuda.synchronize(); th = time.perf_counter()
-        inter_all, _summary = ro.text_env_eval(n_b2 * B, seed_generator=gen_seeds, concurrent=3, **kwf)
-        tev2_s = time.perf_counter() - th
-        tev["three_batches_in_flight"] = dict(value=round(sum(len(ep) for ep in inter_all) / tev2_s, 1), unit="env-steps/s", episode_batches=n_b2,
-                                            ms_per_batch=round(tev2_s * 1e3 / n_b2, 2),
-                                            note="text_env_eval(n_rollouts = 12 x B, concurrent=3): batches k .. k + 2 run at once on three HIP streams "
-                                                 "(3 x B envs in flight; the headline `value` stays one batch of B); tools/bench_text_env_eval_lanes.py: 1 / 2 / 3 lanes")
-        del inter_all
-
-    ms, work, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()
-
-    def read_tag(tag):
-        _lib.check(L.lmrl_prof_read(tag_ids[tag], ctypes.byref(ms), ctypes.byref(work), ctypes.byref(n)))
-        hbm = tag.startswith("attention")
-        rate = (work.value / (ms.value * 1e-3)) / (1e9 if hbm else 1e12) if ms.value > 0 else 0.0
-        peak = HBM_PEAK_GBS if hbm else MFMA_BF16_DENSE_PEAK_TFLOPS
-        return dict(bound="hbm" if hbm else "mfma", kernel=tag, achieved=round(rate, 1), peak=peak,
-                    unit="GB/s" if hbm else "TFLOP/s", frac=round(rate / peak, 4), traffic=None, launches=int(n.value),
-                    avg_launch_us=round(ms.value * 1e3 / max(n.value, 1), 2), share_of_step_time=round(ms.value * 1e-3 / dt, 3))
-
-    if args.graph:
-        # hipGraph replays cannot carry per-kernel event brackets: the roofline kernel is timed in eager episodes of the
-        # same workload run right after the timed region, in this process (same launches, same data).
-        L.lmrl_prof_reset(); L.lmrl_prof_enable(1 << tag_ids[ROOFLINE_TAG])
-        torch.cuda.synchronize(); tb = time.perf_counter()
-        for i in range(2):
-            episode(args.warmup + i, False, eager=True)
-        torch.cuda.synchronize(); dt_keep, dt = dt, time.perf_counter() - tb
-        L.lmrl_prof_enable(0)
-        roofline = read_tag(ROOFLINE_TAG)
-        roofline["timed_in"] = "2 eager episodes after the graph-replayed timed region"
-        dt = dt_keep
-    else:
-        roofline = read_tag(ROOFLINE_TAG)
-    # HBM traffic per launch from the PMC passes (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate runs of this same
-    # command; gfx950 FETCH_SIZE counts 64 B per 128 B request for wide coalesced loads -> doubled, per the microarch
-    # guide).  Not measurable from inside the process, so the committed summary is reported, with its source.
-    try:
-        pmc = json.load(open(os.path.join(ROOT, PROFILE_PMC)))
-        key = next(k for k in pmc if ROOFLINE_KERNEL in k)
-        live = csrc_digest()
-        if pmc.get("__meta__", {}).get("csrc_digest") != live:
-            # the counters were collected on other kernel sources than the ones running now: refuse to report them as this run's traffic
-            roofline["traffic"] = None
-            roofline["traffic_note"] = (f"{PROFILE_PMC} was collected on kernel sources {str(pmc.get('__meta__', {}).get('csrc_digest'))[:12]}, "
-                                        f"live sources are {live[:12]}: stale, not reported (regenerate with tools/pmc_fetch_write.sh)")
-        else:
-            roofline["traffic"] = round((2.0 * pmc[key]["fetch_kb_avg"] + pmc[key]["write_kb_avg"]) * 1024)
-            roofline["traffic_unit"] = f"bytes per launch (2*FETCH_SIZE + WRITE_SIZE, {PROFILE_PMC}, kernel sources {live[:12]})"
-        roofline["algorithmic_bytes_per_launch"] = round(work.value / max(n.value, 1))
-    except Exception:
-        roofline["traffic"] = None
-    # the committed rocprofv3 --kernel-trace --stats summary of this same command, for cross-checking the live event figure
-    # (events bracket the launch on the stream and therefore include the dispatch gap, ~3 us, that rocprof's kernel
-    # begin/end timestamps do not)
-    try:
-        import csv
-        prof = os.path.join(ROOT, PROFILE_STATS)
-        row = next(r for r in csv.DictReader(open(prof)) if ROOFLINE_KERNEL in r["Name"])
-        roofline["rocprofv3_avg_launch_us"] = round(float(row["AverageNs"]) / 1e3, 2)
-        roofline["rocprofv3_summary"] = PROFILE_STATS
-    except Exception:
-        pass
-    # other kernel classes: one extra, untimed episode with their brackets on (brackets cost ~2 us per launch); the same episode yields
-    # the whole-step algorithmic flop / byte totals of `roofline_step`
-    L.lmrl_prof_reset()
-    step_tags = SECONDARY_TAGS + [ROOFLINE_TAG]
-    mask = 0
-    for tg in step_tags:
-        mask |= 1 << tag_ids[tg]
-    L.lmrl_prof_enable(mask)
-    torch.cuda.synchronize(); tb = time.perf_counter()
-    episode(args.warmup, False, eager=True)
-    torch.cuda.synchronize(); dt_keep, dt = dt, time.perf_counter() - tb
-    L.lmrl_prof_enable(0)
-    roofline_secondary = [read_tag(tg) for tg in SECONDARY_TAGS]
-    dt = dt_keep
-    # whole step: algorithmic flops = every GEMM / LM-head flop of the episode; algorithmic bytes = K/V rows the attention reads (device-
-    # counted, shared prefix once) + the weights each forward has to stream once (bf16 layers per forward, the tied LM head per sampled token)
-    flops = bytes_kv = 0.0
-    for tg in step_tags:
-        _lib.check(L.lmrl_prof_read(tag_ids[tg], ctypes.byref(ms), ctypes.byref(work), ctypes.byref(n)))
-        if tg.startswith("attention"):
-            bytes_kv += work.value
-        else:
-            flops += work.value
-    n_fwd = n_turns * 6 + (0 if args.share_header else 1)                 # forwards over all envs: 5 decode + 1 chunk per turn (+ header chunk)
-    layer_w = cfg.n_layer * (3 * cfg.d_model * cfg.d_model + cfg.d_model * cfg.d_model + 2 * cfg.d_model * cfg.d_ff) * 2
-    bytes_w = n_fwd * layer_w + n_turns * 6 * cfg.vocab_padded * cfg.d_model * 2
-    step_s = dt_keep / args.steps
-    roofline_step = dict(flops=flops, bytes=bytes_kv + bytes_w, tflops=round(flops / step_s / 1e12, 1), tb_per_s=round((bytes_kv + bytes_w) / step_s / 1e12, 3),
-                         frac_mfma_peak=round(flops / step_s / 1e12 / MFMA_BF16_DENSE_PEAK_TFLOPS, 4),
-                         frac_hbm_peak=round((bytes_kv + bytes_w) / step_s / 1e9 / HBM_PEAK_GBS, 4),
-                         note="algorithmic work of one episode (counted in one eager episode of the same workload) / graph-timed ms_per_step")
-
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     steps_all = torch.stack(total_steps_parts).sum() if total_steps_parts else total_steps.clone()
     if use_dist:
@@ -1063,19 +953,6 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         torch.distributed.all_reduce(steps_all, op=torch.distributed.ReduceOp.SUM)
     dt_max, n_env_steps = float(t.item()), int(steps_all.item())
-
-    if args.breakdown and rank == 0:
-        L.lmrl_prof_reset(); L.lmrl_prof_enable(0xFFFFFFFF)
-        torch.cuda.synchronize(); tb = time.perf_counter()
-        episode(n_eps - 1, False, eager=True)
-        torch.cuda.synchronize(); te = time.perf_counter() - tb
-        L.lmrl_prof_enable(0)
-        print(f"[breakdown] one episode with every tag bracketed: {te * 1e3:.2f} ms", file=sys.stderr)
-        for name, tid in tag_ids.items():
-            _lib.check(L.lmrl_prof_read(tid, ctypes.byref(ms), ctypes.byref(work), ctypes.byref(n)))
-            if n.value:
-                rate = f"{work.value / (ms.value * 1e-3) / 1e12:8.1f} T(FLOP|B)/s" if work.value > 0 else ""
-                print(f"[breakdown] {name:22s} {n.value:6d} launches {ms.value:9.3f} ms  avg {ms.value * 1e3 / n.value:8.2f} us {rate}", file=sys.stderr)
 
     if rank == 0:
         out = {
@@ -1089,23 +966,158 @@ def main():
                                    f"{B} lock-step envs per GPU, {n_turns} turns x <=6 generated tokens, vocab {args.vocab_file}",
                        "envs_per_gpu": B, "hip_streams": S, "hip_graph": bool(args.graph), "shared_header_prefill": bool(args.share_header), "max_new_tokens": 6, "parallelism": f"env-sharded x{world}, no data-path collective",
                        "env_steps_timed": n_env_steps},
-            "roofline": roofline, "roofline_secondary": roofline_secondary, "roofline_step": roofline_step,
-            "host_materialise_ms": round(host_materialise_ms, 2),
-            "host_materialise_note": f"rank 0, one episode batch: device->host copy of the records + {n_trans} InteractionTransition objects built in "
-                                     "Python (what text_env_eval returns); not inside `value`, which ends on the device",
-            "value_incl_host_materialise": round(n_env_steps / (dt_max + args.steps * host_materialise_ms * 1e-3), 1),
-            "text_env_eval": tev,
         }
         if dist_info is not None:     # N > 1 (or a forced 1-rank group): what the process group itself reports (the N = 1 line is unchanged)
             out["dist"] = dist_info
             out["backend"], out["world_size"], out["rccl_version"] = dist_info["backend"], dist_info["world_size"], dist_info["rccl_version"]
+    ms, work, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()      # lmrl_prof_read outputs (--full legs, --breakdown)
+    # the legs below run under --full only (--breakdown aside): a plain run prints the headline fields above and nothing else
+    if args.full:
+        # what a drop-in caller of `text_env_eval` pays on top of the device episode (LLM_RL/environment.py:211-267 returns HOST lists of
+        # InteractionTransition): device -> host copy of the records + building the Python objects for this rank's B envs.  Outside `value`.
+        th = time.perf_counter()
+        n_trans = sum(len(ep) for r in ros for ep in r.interactions())
+        host_materialise_ms = (time.perf_counter() - th) * 1e3
+        # ... and the public call itself on the same steered workload: `WordleRolloutEngine.text_env_eval` over 4 episode batches (graph
+        # replays; the host builds batch k's transition lists while the device runs batch k + 1), env steps returned / wall time
+        tev = None
+        if S == 1:
+            n_b = min(4, n_eps)
+            gen_seeds = iter(range(10 ** 6, 10 ** 9))
+            kwf = dict(scripted_guesses_fn=lambda bid: guesses[bid % n_eps], steer_strength=30.0, temperature=1.0, sample_seed=9, use_graph=True)
+            ro.text_env_eval(B, seed_generator=gen_seeds, **kwf)       # warm: pinned buffers, graph capture
+            torch.cuda.synchronize(); th = time.perf_counter()
+            inter_all, _summary = ro.text_env_eval(n_b * B, seed_generator=gen_seeds, **kwf)
+            tev_s = time.perf_counter() - th
+            tev = dict(value=round(sum(len(ep) for ep in inter_all) / tev_s, 1), unit="env-steps/s", episode_batches=n_b, ms_per_batch=round(tev_s * 1e3 / n_b, 2),
+                       note="rank 0: WordleRolloutEngine.text_env_eval(n_rollouts = 4 x B) end to end — device episodes (hipGraph replays) + host lists of "
+                            "InteractionTransition + summary dict, host materialisation of batch k overlapped with the device work of batch k + 1")
+            del inter_all
+            # three episode batches in flight (concurrent=3: twin engines — own KV cache, env state, graph — on their own HIP streams over the same
+            # weights): each batch is still one lock-step batch of B envs; the dependent launch chains fill each other's gaps on the 256 CUs
+            n_b2 = 12
+            ro.text_env_eval(3 * B, seed_generator=gen_seeds, concurrent=3, **kwf)      # warm: twin engines, their graphs, pinned buffers
+            torch.cuda.synchronize(); th = time.perf_counter()
+            inter_all, _summary = ro.text_env_eval(n_b2 * B, seed_generator=gen_seeds, concurrent=3, **kwf)
+            tev2_s = time.perf_counter() - th
+            tev["three_batches_in_flight"] = dict(value=round(sum(len(ep) for ep in inter_all) / tev2_s, 1), unit="env-steps/s", episode_batches=n_b2,
+                                                ms_per_batch=round(tev2_s * 1e3 / n_b2, 2),
+                                                note="text_env_eval(n_rollouts = 12 x B, concurrent=3): batches k .. k + 2 run at once on three HIP streams "
+                                                     "(3 x B envs in flight; the headline `value` stays one batch of B); tools/bench_text_env_eval_lanes.py: 1 / 2 / 3 lanes")
+            del inter_all
+
+        def read_tag(tag):
+            _lib.check(L.lmrl_prof_read(tag_ids[tag], ctypes.byref(ms), ctypes.byref(work), ctypes.byref(n)))
+            hbm = tag.startswith("attention")
+            rate = (work.value / (ms.value * 1e-3)) / (1e9 if hbm else 1e12) if ms.value > 0 else 0.0
+            peak = HBM_PEAK_GBS if hbm else MFMA_BF16_DENSE_PEAK_TFLOPS
+            return dict(bound="hbm" if hbm else "mfma", kernel=tag, achieved=round(rate, 1), peak=peak,
+                        unit="GB/s" if hbm else "TFLOP/s", frac=round(rate / peak, 4), traffic=None, launches=int(n.value),
+                        avg_launch_us=round(ms.value * 1e3 / max(n.value, 1), 2), share_of_step_time=round(ms.value * 1e-3 / dt, 3))
+
+        if args.graph:
+            # hipGraph replays cannot carry per-kernel event brackets: the roofline kernel is timed in eager episodes of the
+            # same workload run right after the timed region, in this process (same launches, same data).
+            L.lmrl_prof_reset(); L.lmrl_prof_enable(1 << tag_ids[ROOFLINE_TAG])
+            torch.cuda.synchronize(); tb = time.perf_counter()
+            for i in range(2):
+                episode(args.warmup + i, False, eager=True)
+            torch.cuda.synchronize(); dt_keep, dt = dt, time.perf_counter() - tb
+            L.lmrl_prof_enable(0)
+            roofline = read_tag(ROOFLINE_TAG)
+            roofline["timed_in"] = "2 eager episodes after the graph-replayed timed region"
+            dt = dt_keep
+        else:
+            roofline = read_tag(ROOFLINE_TAG)
+        # HBM traffic per launch from the PMC passes (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate runs of this same
+        # command; gfx950 FETCH_SIZE counts 64 B per 128 B request for wide coalesced loads -> doubled, per the microarch
+        # guide).  Not measurable from inside the process, so the committed summary is reported, with its source.
+        try:
+            pmc = json.load(open(os.path.join(ROOT, PROFILE_PMC)))
+            key = next(k for k in pmc if ROOFLINE_KERNEL in k)
+            live = csrc_digest()
+            if pmc.get("__meta__", {}).get("csrc_digest") != live:
+                # the counters were collected on other kernel sources than the ones running now: refuse to report them as this run's traffic
+                roofline["traffic"] = None
+                roofline["traffic_note"] = (f"{PROFILE_PMC} was collected on kernel sources {str(pmc.get('__meta__', {}).get('csrc_digest'))[:12]}, "
+                                            f"live sources are {live[:12]}: stale, not reported (regenerate with tools/pmc_fetch_write.sh)")
+            else:
+                roofline["traffic"] = round((2.0 * pmc[key]["fetch_kb_avg"] + pmc[key]["write_kb_avg"]) * 1024)
+                roofline["traffic_unit"] = f"bytes per launch (2*FETCH_SIZE + WRITE_SIZE, {PROFILE_PMC}, kernel sources {live[:12]})"
+            roofline["algorithmic_bytes_per_launch"] = round(work.value / max(n.value, 1))
+        except Exception:
+            roofline["traffic"] = None
+        # the committed rocprofv3 --kernel-trace --stats summary of this same command, for cross-checking the live event figure
+        # (events bracket the launch on the stream and therefore include the dispatch gap, ~3 us, that rocprof's kernel
+        # begin/end timestamps do not)
+        try:
+            import csv
+            prof = os.path.join(ROOT, PROFILE_STATS)
+            row = next(r for r in csv.DictReader(open(prof)) if ROOFLINE_KERNEL in r["Name"])
+            roofline["rocprofv3_avg_launch_us"] = round(float(row["AverageNs"]) / 1e3, 2)
+            roofline["rocprofv3_summary"] = PROFILE_STATS
+        except Exception:
+            pass
+        # other kernel classes: one extra, untimed episode with their brackets on (brackets cost ~2 us per launch); the same episode yields
+        # the whole-step algorithmic flop / byte totals of `roofline_step`
+        L.lmrl_prof_reset()
+        step_tags = SECONDARY_TAGS + [ROOFLINE_TAG]
+        mask = 0
+        for tg in step_tags:
+            mask |= 1 << tag_ids[tg]
+        L.lmrl_prof_enable(mask)
+        torch.cuda.synchronize(); tb = time.perf_counter()
+        episode(args.warmup, False, eager=True)
+        torch.cuda.synchronize(); dt_keep, dt = dt, time.perf_counter() - tb
+        L.lmrl_prof_enable(0)
+        roofline_secondary = [read_tag(tg) for tg in SECONDARY_TAGS]
+        dt = dt_keep
+        # whole step: algorithmic flops = every GEMM / LM-head flop of the episode; algorithmic bytes = K/V rows the attention reads (device-
+        # counted, shared prefix once) + the weights each forward has to stream once (bf16 layers per forward, the tied LM head per sampled token)
+        flops = bytes_kv = 0.0
+        for tg in step_tags:
+            _lib.check(L.lmrl_prof_read(tag_ids[tg], ctypes.byref(ms), ctypes.byref(work), ctypes.byref(n)))
+            if tg.startswith("attention"):
+                bytes_kv += work.value
+            else:
+                flops += work.value
+        n_fwd = n_turns * 6 + (0 if args.share_header else 1)                 # forwards over all envs: 5 decode + 1 chunk per turn (+ header chunk)
+        layer_w = cfg.n_layer * (3 * cfg.d_model * cfg.d_model + cfg.d_model * cfg.d_model + 2 * cfg.d_model * cfg.d_ff) * 2
+        bytes_w = n_fwd * layer_w + n_turns * 6 * cfg.vocab_padded * cfg.d_model * 2
+        step_s = dt_keep / args.steps
+        roofline_step = dict(flops=flops, bytes=bytes_kv + bytes_w, tflops=round(flops / step_s / 1e12, 1), tb_per_s=round((bytes_kv + bytes_w) / step_s / 1e12, 3),
+                             frac_mfma_peak=round(flops / step_s / 1e12 / MFMA_BF16_DENSE_PEAK_TFLOPS, 4),
+                             frac_hbm_peak=round((bytes_kv + bytes_w) / step_s / 1e9 / HBM_PEAK_GBS, 4),
+                             note="algorithmic work of one episode (counted in one eager episode of the same workload) / graph-timed ms_per_step")
+        if rank == 0:
+            out.update({
+                "roofline": roofline, "roofline_secondary": roofline_secondary, "roofline_step": roofline_step,
+                "host_materialise_ms": round(host_materialise_ms, 2),
+                "host_materialise_note": f"rank 0, one episode batch: device->host copy of the records + {n_trans} InteractionTransition objects built in "
+                                         "Python (what text_env_eval returns); not inside `value`, which ends on the device",
+                "value_incl_host_materialise": round(n_env_steps / (dt_max + args.steps * host_materialise_ms * 1e-3), 1),
+                "text_env_eval": tev,
+            })
+    if args.breakdown and rank == 0:
+        L.lmrl_prof_reset(); L.lmrl_prof_enable(0xFFFFFFFF)
+        torch.cuda.synchronize(); tb = time.perf_counter()
+        episode(n_eps - 1, False, eager=True)
+        torch.cuda.synchronize(); te = time.perf_counter() - tb
+        L.lmrl_prof_enable(0)
+        print(f"[breakdown] one episode with every tag bracketed: {te * 1e3:.2f} ms", file=sys.stderr)
+        for name, tid in tag_ids.items():
+            _lib.check(L.lmrl_prof_read(tid, ctypes.byref(ms), ctypes.byref(work), ctypes.byref(n)))
+            if n.value:
+                rate = f"{work.value / (ms.value * 1e-3) / 1e12:8.1f} T(FLOP|B)/s" if work.value > 0 else ""
+                print(f"[breakdown] {name:22s} {n.value:6d} launches {ms.value:9.3f} ms  avg {ms.value * 1e3 / n.value:8.2f} us {rate}", file=sys.stderr)
+
     for r in ros:
         r.close()
     del ros, ro, eng
     import gc
     gc.collect()
     torch.cuda.empty_cache()
-    if not args.no_fp32_mode:
+    if args.full and not args.no_fp32_mode:
         # the reference's DEFAULT rollout arithmetic (eval_bc_gpt2.py:34,69: float32): the same workload on GPT2EngineF32 — fp32 weights,
         # activations and K/V cache, exact-fp32 MFMA products, materialised fp32 logits, same sampler and env kernels; eager launches.
         # Its every sampled token is pinned to the float64 oracle in tests/test_gpu_f32_engine.py.  Reported beside `value`, never as it.
@@ -1152,7 +1164,7 @@ def main():
             del rof, engf
             gc.collect()
             torch.cuda.empty_cache()
-    if not args.no_train_step:
+    if args.full and not args.no_train_step:
         # the gradient step of the path (configs[2]): ILQL M3 in the reference's default fp32 arithmetic and in its optional bf16-matmul mode;
         # for N > 1 every rank takes part (data parallel, one gradient all-reduce per step over RCCL)
         ts = {}
@@ -1160,21 +1172,21 @@ def main():
             ts["ilql_" + mm] = run_train_step("ilql-step", mm, args.train_batch, args.train_steps, 2, dev, rank, world, use_dist, backend)
         if rank == 0:
             out["train_step"] = ts
-    if rank == 0 and not args.no_rl_reduce:
+    if args.full and rank == 0 and not args.no_rl_reduce:
         out["rl_reduce"] = run_rl_reduce(dev)
-    if rank == 0 and world == 1 and not args.no_maze and S == 1 and args.graph and n_eps >= 4:
+    if args.full and rank == 0 and world == 1 and not args.no_maze and S == 1 and args.graph and n_eps >= 4:
         try:
             out["sampling_warpers"] = run_warpers(vocab, guesses, seeds_all, B, dev)
         except Exception as e:              # informational leg: never fails the line
             out["sampling_warpers"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         gc.collect(); torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_maze and S == 1 and args.graph:
+    if args.full and rank == 0 and world == 1 and not args.no_maze and S == 1 and args.graph:
         try:
             out["maze_rollout"] = run_maze_rollout(dev)
         except Exception as e:              # informational leg: never fails the line
             out["maze_rollout"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         gc.collect(); torch.cuda.empty_cache()
-    if not args.no_ppo_iteration and S == 1 and args.graph:
+    if args.full and not args.no_ppo_iteration and S == 1 and args.graph:
         # the online loop end to end (rollouts -> PPO data -> train steps -> weights back into the engine), device-resident, in the headline's bf16
         # mode and in the reference's default fp32 arithmetic; the host-array path of the same iteration beside the bf16 one
         pi = {}
@@ -1189,24 +1201,24 @@ def main():
         if rank == 0:
             out["ppo_iteration"] = pi
     if rank == 0:
-        if world == 1 and not args.no_batch_sweep and not args.no_cpu_baseline and B == 1024 and S == 1 and args.graph:       # the full default line only (the profiling tools pass --no-cpu-baseline)
+        if args.full and world == 1 and not args.no_batch_sweep and not args.no_cpu_baseline and B == 1024 and S == 1 and args.graph:   # the whole --full line only (the profiling tools pass --no-cpu-baseline)
             # the same engine, kernels and timed region at 4096 envs per GPU (a child process: this one's sessions and graphs stay as they are).  Not the
             # metric's configuration (1024 envs) — reported because the roofline kernel's fraction is a function of the launch size: north_star's
             # ">= 100 k env-steps/s at >= 60 % of the HBM roofline" holds together from 4096 envs per GPU up (profiles/r04_bench_batch_sweep.txt)
             import subprocess
             gc.collect(); torch.cuda.empty_cache()
-            out["larger_batches"] = {"note": "python bench.py --batch B: the default line's engine, kernels and timed region at B envs per GPU; NOT the metric's "
+            out["larger_batches"] = {"note": "python bench.py --full --batch B: the headline's engine, kernels and timed region at B envs per GPU; NOT the metric's "
                                              "configuration (1024 envs)"}
             for b_ in (4096, 8192):
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", str(b_), "--steps", "4", "--warmup", "1", "--no-train-step", "--no-fp32-mode",
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--batch", str(b_), "--steps", "4", "--warmup", "1", "--no-train-step", "--no-fp32-mode",
                                         "--no-cpu-baseline", "--no-batch-sweep", "--no-ppo-iteration", "--no-rl-reduce", "--no-maze"], capture_output=True, text=True, timeout=240)
                     d4 = json.loads(r.stdout.strip().splitlines()[-1])
                     out["larger_batches"][str(b_)] = {"value": d4["value"], "unit": d4["unit"], "ms_per_step": d4["ms_per_step"], "steps": d4["steps"],
                                                       "roofline_frac": d4["roofline"]["frac"], "roofline_kernel": d4["roofline"]["kernel"]}
                 except Exception as e:       # informational leg: never fails the line
                     out["larger_batches"][str(b_)] = {"error": f"{type(e).__name__}: {e}"[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(vocab.all_vocab)
             out["env_only"] = gpu_env_only(vocab, dev)
         print(json.dumps(out), flush=True)

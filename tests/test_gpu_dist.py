@@ -210,9 +210,10 @@ def test_two_ranks_half_batch_equal_one_rank_full_batch(tmp_path):
 
 
 def test_bench_gpus_2_spawns_two_ranks_and_reports_the_train_step():
-    """the plain driver command `python bench.py --gpus 2 ...` must itself launch 2 ranks (torch.distributed.run, one
+    """the driver command `python bench.py --gpus 2 --full ...` must itself launch 2 ranks (torch.distributed.run, one
     process per GPU; on this 1-GPU tier the ranks share the GPU, which the bench refuses unless LMRL_BENCH_BACKEND=gloo is explicit) and rank 0 must print ONE JSON line with
-    n_gpus = 2 whose `train_step` object carries the ILQL step with its gradient all-reduce (bytes, exposed time)."""
+    n_gpus = 2 whose `train_step` object carries the ILQL step with its gradient all-reduce (bytes, exposed time).  The train step and the other
+    legs checked here are `--full` legs: a plain run prints the headline only."""
     import json
     import os
     import subprocess
@@ -226,7 +227,7 @@ def test_bench_gpus_2_spawns_two_ranks_and_reports_the_train_step():
         assert r0.returncode != 0 and "LMRL_BENCH_BACKEND=gloo" in (r0.stderr + r0.stdout), (r0.returncode, r0.stderr[-1500:])
         assert not [ln for ln in r0.stdout.splitlines() if ln.startswith("{")]
         env["LMRL_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "64",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "1", "--batch", "64",
                         "--train-batch", "2", "--train-steps", "1", "--no-cpu-baseline", "--ppo-iters", "1", "--ppo-train-steps", "1", "--ppo-max-length", "192"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -327,3 +327,36 @@ def test_persistent_lm_head_equals_one_tile_per_workgroup_kernel(small):
             assert torch.equal(a[0], b[0])
             assert (a[1] is None and b[1] is None) or torch.equal(a[1], b[1])
             assert (a[2] is None and b[2] is None) or torch.equal(a[2], b[2])
+
+
+def test_plain_bench_run_prints_the_headline_and_times_what_full_times(tmp_path):
+    """`bench.py` without `--full` prints the headline fields and nothing else; with `--full` the same line carries the other legs on top of
+    the SAME timed steps: same seeded inputs, same env steps timed, same records written by --dump-outputs.  Small batch, one step: a
+    launch-path check, not a measurement."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = {"plain": [], "full": ["--full", "--no-cpu-baseline", "--no-train-step", "--no-fp32-mode", "--no-ppo-iteration", "--no-rl-reduce", "--no-maze"]}
+    lines = {}
+    for name, extra in runs.items():
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "64",
+                            "--dump-outputs", str(tmp_path / name)] + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (name, r.stderr[-3000:])
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, (name, r.stdout[-2000:])
+        lines[name] = json.loads(js[0])
+    plain, full = lines["plain"], lines["full"]
+    headline = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+                "dtype_note", "config"}
+    assert set(plain) == headline, sorted(set(plain) ^ headline)
+    assert headline < set(full) and {"roofline", "roofline_secondary", "roofline_step", "host_materialise_ms", "text_env_eval"} <= set(full)
+    for k in headline - {"value", "ms_per_step"}:
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"]["env_steps_timed"] >= 64
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names and names == sorted(os.listdir(tmp_path / "full"))
+    for f in names:
+        a, b = np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)
+        assert a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True), f

@@ -1,5 +1,6 @@
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d /tmp/pmc1 -- python /root/repo/bench.py --graph 0 --steps 1 --warmup 1 --no-cpu-baseline > /root/repo/gpurun_out/pmc1.log 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d /tmp/pmc1 -- python "$REPO/bench.py" --full --graph 0 --steps 1 --warmup 1 --no-cpu-baseline > /tmp/pmc1.log 2>&1
 f=$(find /tmp/pmc1 -name "*counter_collection.csv" | head -1); ls -la $f
 python - $f <<'PY'
 import csv,sys,collections

@@ -743,6 +743,103 @@ int lmrl_maze_tok_result(lmrl_maze_tok_ctx *c, const lmrl_maze_traj *tr, const f
                          const uint8_t *kind_d, int n, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * On-device token <-> game bookkeeping for lock-step chess rollouts (csrc/chess_tokens.hip) around the rules of csrc/chess_rules.h: the chess
+ * twin of the Maze loop above for `FenChessHistoryEnv` (chess/env/env.py:213-238; the online PPO script chess/ppo/train_ppo_gpt2_online.py:201-340).
+ * A turn's prompt is `' '.join(fen)` of the current position alone (preprocess_state_og): no history window, no prefix cache — only the K/V
+ * rows of the prefix the prompt shares with the previous turn's are kept (lmrl_chess_tok_prefix).  Replaces the
+ * per-turn host work of interact_environment + GPT2PPOPolicy.act + VectorChessEnv.step.  Every buffer is the caller's; all calls are asynchronous
+ * on `stream`.  One game per lane.  N envs, T = max_turns, G = max_new_tokens; strings are fixed-pitch and NUL-padded as above.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    /* the episode record, one row per (env, turn) */
+    char *fen;            /* [N][T][LMRL_CHESS_FEN_BYTES] position text the turn's prompt was rendered from (turn 0: the start position as given) */
+    int32_t *gen;         /* [N][T][G] generated ids of the turn's action */
+    int32_t *gen_len;     /* [N][T] */
+    char *action;         /* [N][T][LMRL_CHESS_ACTION_BYTES] the SAN string handed to the board */
+    uint8_t *result;      /* [N][T] LMRL_CHESS_ILLEGAL .. LMRL_CHESS_NULL_MOVE */
+    float *reward;        /* [N][T] after the opponent's half (-1: the agent was mated) */
+    uint8_t *done;        /* [N][T] game over, or more than max_moves agent moves made */
+    char *opp_san;        /* [N][T][LMRL_CHESS_ACTION_BYTES] the opponent's reply in SAN ("" when there was none) */
+    char *reply;          /* [N][T][8] the same reply in UCI form */
+    int32_t *n_turns;     /* [N] env steps taken */
+    uint8_t *live;        /* [N] episode still running */
+    float *ep_reward;     /* [N] */
+    /* the current turn */
+    char *cur_fen;        /* [N][LMRL_CHESS_FEN_BYTES] the observation the next prompt is rendered from */
+    int32_t *cur_len;     /* [N] its length */
+    char *prev_fen;       /* [N][LMRL_CHESS_FEN_BYTES] the observation of the previous turn's prompt (its K/V rows are still in the cache) */
+    int32_t *prev_len;    /* [N] its length (0: none) */
+    int32_t *keep;        /* [N] prompt tokens of the current turn whose K/V rows are kept from the previous turn (lmrl_chess_tok_prefix) */
+    int32_t *out_tok;     /* [N][G] generation buffer (lmrl_gen_accept) */
+    int32_t *out_len;     /* [N] */
+    uint8_t *gen_active;  /* [N] */
+    char *act;            /* [N][LMRL_CHESS_ACTION_BYTES] the decoded action */
+    uint8_t *res;         /* [N] result of the agent's half-step (255: env not stepping) */
+    float *rew;           /* [N] */
+    uint8_t *dn;          /* [N] */
+    char *uci;            /* [N][8] the agent's move in UCI form where a reply is wanted (result MOVED), "" elsewhere: what goes DOWN to a host engine */
+    char *cur_reply;      /* [N][8] the reply in UCI form: written by lmrl_chess_tok_opponent, or by the caller before lmrl_chess_tok_opponent_host */
+    uint8_t *reply_ok;    /* [N] 0: the reply was not a legal move of the position */
+    char *cur_san;        /* [N][LMRL_CHESS_ACTION_BYTES] */
+    int32_t *flags;       /* [1] bit 0: a prompt was longer than the chunks scheduled for it (lmrl_chess_tok_prompt) */
+} lmrl_chess_traj;
+
+typedef struct lmrl_chess_tok_ctx lmrl_chess_tok_ctx;
+/* byte_id (host, [256]): the id of every single-byte string (-1: none) — a prompt is `tokenizer.encode(' '.join(fen))` for tokenizers that encode
+ * that text character by character (the caller probes it).  tok_bytes [vocab][16] / tok_blen [vocab]: as lmrl_maze_tok_create.  byte_ids != 0: ids
+ * 0..255 ARE the text's UTF-8 bytes and every other id decodes to nothing (then a generation is decoded as UTF-8 with Python's errors="ignore").
+ * eos_token < 0: none.  max_turns < 4096.  host_only != 0: no device tables — only the lmrl_chess_host_* faces below work (CPU tests). */
+lmrl_chess_tok_ctx *lmrl_chess_tok_create(const int32_t *byte_id, const uint8_t *tok_bytes, const uint8_t *tok_blen, int vocab, int byte_ids, int eos_token,
+                                          int max_new_tokens, int max_turns, int host_only);
+void lmrl_chess_tok_destroy(lmrl_chess_tok_ctx *c);
+/* episode start: chess.Board(fen) for every env from fens_d [n][LMRL_CHESS_FEN_BYTES] (ok_d[i] = 0: malformed, env not live), records cleared, the
+ * start text becomes the first observation */
+int lmrl_chess_tok_begin(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, void *pos_d, const char *fens_d, uint8_t *ok_d, int n, void *stream);
+/* turn start: how much of the cache survives.  The caches still hold the previous turn's prompt at positions [0, its length); with reuse != 0 the
+ * K/V rows of the longest common prefix of the previous and the current (left-truncated) prompt are kept, at least one token is forwarded again —
+ * the rule of the generic policy's prefill (`GPT2PPOPolicy(reuse_kv=True)`): after an illegal move the position and so the prompt is unchanged
+ * and one token goes through the model, after a move the rows up to the first changed square stay.  len_d [N]: the KV session's cache lengths,
+ * set to keep[env] (0 with reuse == 0, on an episode's first turn, and for finished envs). */
+int lmrl_chess_tok_prefix(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, int max_input_length, int reuse, int32_t *len_d, int n, void *stream);
+/* chunk j of n_chunks (chunk tokens per env) of the part of the current prompts (left-truncated to max_input_length tokens) behind the kept prefix,
+ * for a prefill forward: chunk_tok_d [N][chunk], chunk_cnt_d [N] (0 for finished envs).  A prompt that does not fit n_chunks * chunk tokens sets
+ * flags bit 0. */
+int lmrl_chess_tok_prompt(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, int j, int chunk, int max_input_length, int n_chunks, int32_t *chunk_tok_d,
+                          int32_t *chunk_cnt_d, int n, void *stream);
+/* generated ids (out_tok / out_len) -> the SAN string of the host path: ids up to the first eos -> text (special ids skipped) -> the policy's
+ * `removesuffix('\n') + '\n'` -> postprocess_move (every ' ' removed, then str.strip()) -> non-ASCII characters as '?', at most
+ * LMRL_CHESS_ACTION_BYTES - 1 bytes (VectorChessBoards._strings); then the agent's half of ChessEnv.step: res / rew / dn / uci */
+int lmrl_chess_tok_action(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, void *pos_d, int n, void *stream);
+/* the device opponent, for games whose result is LMRL_CHESS_MOVED: one of the position's legal moves (lmrl_chess_describe's order) is played.
+ * reply_idx_d == NULL: the counter-based reply stream — legal_moves[(word * count) >> 32] with
+ *     word = first output word of Philox4x32-7 (the sampler's function: csrc/sampler.hip, oracle/gpt2.py `philox4x32_10(..., rounds=7)`),
+ *     counter = (env, turn of the env, LMRL_CHESS_REPLY_STREAM, *epoch_d [0 when NULL]), key = (seed low word, seed high word);
+ * epoch_d is read on the device when the kernel runs, so a captured turn draws fresh replies on every replay (the caller advances it, as the
+ * sampler's epoch).  A stream of this package's own: the reference draws from numpy's global state in env order (env.py:178).
+ * reply_idx_d != NULL (int32 [reply_turns][n]): legal_moves[reply_idx[min(turn, reply_turns - 1)][env] mod count] (scripted workloads, tests). */
+#define LMRL_CHESS_REPLY_STREAM 0x43484553u
+int lmrl_chess_tok_opponent(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, void *pos_d, uint64_t seed, const uint32_t *epoch_d, const int32_t *reply_idx_d,
+                            int reply_turns, int n, void *stream);
+/* the host opponent (a UCI engine pool): the caller read tr->uci and wrote the replies into tr->cur_reply; reply_ok = 0 for an illegal one */
+int lmrl_chess_tok_opponent_host(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, void *pos_d, int n, void *stream);
+/* the turn into the record, the next observation (board.fen()), counters, live / gen_active for the next turn; done also once more than max_moves
+ * agent moves were made (FenChessHistoryEnv) */
+int lmrl_chess_tok_result(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, const void *pos_d, int max_moves, int n, void *stream);
+/* The finished episodes of the first n envs as PPO records (lmrl_ppo_records), the twin of lmrl_maze_tok_ppo_records: one token trajectory per
+ * transition — the (untruncated) prompt ids of the observation ++ the action ids, the reward on the action's last token — chained per episode as
+ * chess/ppo/train_ppo_gpt2_online.py:293-314 builds them.  Action ids = the encoding of the action TEXT `decode(ids).removesuffix('\n') + '\n'`:
+ * byte ids: the UTF-8 bytes of the decoded characters; otherwise the generated ids up to eos minus special ids; newline_tok appended when the text
+ * does not end in a newline.  off_d [n + 1] = exclusive scan of tr->n_turns. */
+int lmrl_chess_tok_ppo_records(lmrl_chess_tok_ctx *c, const lmrl_chess_traj *tr, int n, const int32_t *off_d, int newline_tok, int cap, int32_t *tokens_d,
+                               uint8_t *is_action_d, float *reward_d, int32_t *n_tok_d, int32_t *chain_d, int32_t *pos_d, uint8_t *last_d, uint8_t *done_d,
+                               int32_t *chain_total_d, void *stream);
+/* host faces of the string work (the same functions on host memory; no GPU needed): the prompt ids of a position text (-> count, -1: out_cap too
+ * small), the action bytes of a generation (out: LMRL_CHESS_ACTION_BYTES bytes, -> length), one word of the reply stream */
+int lmrl_chess_host_prompt_tokens(const lmrl_chess_tok_ctx *c, const char *fen, int max_input_length, int32_t *out, int out_cap);
+int lmrl_chess_host_action_from_tokens(const lmrl_chess_tok_ctx *c, const int32_t *ids, int n, char *out);
+uint32_t lmrl_chess_host_reply_word(uint64_t seed, uint32_t epoch, uint32_t turn, uint32_t env);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the live roofline figure).
  * mask bit t enables tag t; `work` accumulates the algorithmic flops (GEMM-class tags) or bytes (others) per launch.
  * ------------------------------------------------------------------------------------------ */

@@ -120,6 +120,19 @@ _SIGS = {
     "lmrl_chess_host_agent_step": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_void_p]),
     "lmrl_chess_host_opponent_step": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_void_p, c_void_p]),
     "lmrl_chess_host_status": (c_int, [c_void_p]),
+    "lmrl_chess_tok_create": (c_void_p, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "lmrl_chess_tok_destroy": (None, [c_void_p]),
+    "lmrl_chess_tok_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_chess_tok_prefix": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "lmrl_chess_tok_prompt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_chess_tok_action": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_chess_tok_opponent": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lmrl_chess_tok_opponent_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_chess_tok_result": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lmrl_chess_tok_ppo_records": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 10),
+    "lmrl_chess_host_prompt_tokens": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_void_p, c_int]),
+    "lmrl_chess_host_action_from_tokens": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_chess_host_reply_word": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "lmrl_wordle_tok_create": (c_void_p, [c_void_p, c_void_p, c_int, c_int, c_int]),
     "lmrl_wordle_tok_destroy": (None, [c_void_p]),
     "lmrl_wordle_tok_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -3,6 +3,7 @@
     python scripts/harness.py ilql     --train-data d.jsonl [--eval-data e.jsonl]    # llm_rl_scripts/wordle/ilql/train_ilql_gpt2.py
     python scripts/harness.py ppo      [--bc-data d.jsonl]                           # llm_rl_scripts/wordle/ppo/train_ppo_gpt2.py
     python scripts/harness.py ppo      --env maze --device-rollouts 1                # llm_rl_scripts/maze/ppo/train_ppo_online.py (device-resident loop)
+    python scripts/harness.py ppo      --env chess --device-rollouts 1               # llm_rl_scripts/chess/ppo/train_ppo_gpt2_online.py (device-resident loop)
     python scripts/harness.py bc-eval                                                # llm_rl_scripts/wordle/bc/eval_bc_gpt2.py
     python scripts/harness.py maze-eval                                              # llm_rl_scripts/maze/bc/fully_observed_bc.py (eval part)
     python scripts/harness.py gen-data --n-data 1000 --out d.jsonl                   # llm_rl_scripts/wordle/misc/data_gen.py
@@ -210,8 +211,6 @@ def cmd_ppo(a):
     bc = DS.MaskDataset.from_jsonl(a.bc_data, tok, bs) if a.bc_data else None
     if a.env == "chess":        # configs[3]: online PPO against the chess env (chess/ppo/train_ppo_gpt2_online.py:201-222)
         from lmrl_gym_amd.envs import chess as C
-        if a.device_rollouts:
-            raise SystemExit("--device-rollouts is the Wordle token loop; the chess env steps its boards on the device through the text protocol")
         start = C.large_piece_random_endgame(a.chess_pieces) if a.chess_pieces else None
         env = C.FenChessHistoryEnv(max_moves=a.chess_max_moves, from_position=start, random_opponent=bool(a.chess_random_opponent),
                                    **({} if a.chess_random_opponent else dict(engine_path=a.chess_engine, engine_options={"Use NNUE": a.chess_use_nnue},
@@ -228,7 +227,15 @@ def cmd_ppo(a):
     # --device-rollouts: the whole iteration stays in HBM — rollout records -> PPO data -> device batches -> train steps -> the trainer's
     # parameters copied into the engine in place (WordleRolloutEngine.ppo_rollouts, algorithms/ppo_device.py); --resident 0: the host-array path
     resident = bool(a.device_rollouts) and bool(a.resident)
-    if resident and a.env == "maze":
+
+    def chess_rollouts():
+        # env + policy + lock-step loop on the GPU (ChessRolloutEngine): the device opponent for --chess-random-opponent 1, else the env's engine pool
+        from lmrl_gym_amd.chess_rollout import ChessRolloutEngine
+        return ChessRolloutEngine(policy.engine, tok, env, a.rollout_bsize, max_new_tokens=min(a.max_output_length, 12), eos_token_id=tok.encode("\n")[0],
+                                  max_input_length=a.max_input_length, opponent="device" if a.chess_random_opponent else env._vec.engine)
+    if resident and a.env == "chess":
+        ro_res = chess_rollouts()
+    elif resident and a.env == "maze":
         from lmrl_gym_amd.maze_rollout import MazeRolloutEngine
         ro_res = MazeRolloutEngine(policy.engine, tok, env, a.rollout_bsize, max_new_tokens=min(a.max_output_length, 12), eos_token_id=tok.encode("\n")[0],
                                    max_input_length=a.max_input_length)
@@ -238,7 +245,7 @@ def cmd_ppo(a):
         if limit is not None and step >= limit:
             break
         if resident:
-            warp = dict(top_k=int(a.policy_top_k or 0)) if a.env == "maze" else dict(top_k=int(a.policy_top_k or 0), top_p=float(a.policy_top_p or 0.0))
+            warp = dict(top_k=int(a.policy_top_k or 0)) if a.env in ("maze", "chess") else dict(top_k=int(a.policy_top_k or 0), top_p=float(a.policy_top_p or 0.0))
             ds, kls, summary = ro_res.ppo_rollouts(inf, a.n_rollouts, seed_generator=iter(range(rnd * 10 ** 6, 10 ** 9)), gamma=a.gamma, lam=a.lam,
                                                    kl_weight=ctl.value, max_length=max_len, use_advantage_whitening=a.use_advantage_whitening,
                                                    temperature=a.policy_temperature or 1.0, sample_seed=rnd, bsize=max(a.ppo_data_bsize, 64), **warp)
@@ -272,6 +279,11 @@ def cmd_ppo(a):
             from lmrl_gym_amd.maze_rollout import MazeRolloutEngine
             ro = MazeRolloutEngine(policy.engine, tok, env, a.rollout_bsize, max_new_tokens=min(a.max_output_length, 12), eos_token_id=tok.encode("\n")[0],
                                    max_input_length=a.max_input_length)
+            raw, summary = ro.text_env_eval(a.n_rollouts, seed_generator=iter(range(rnd * 10 ** 6, 10 ** 9)), temperature=a.policy_temperature or 1.0,
+                                            top_k=int(a.policy_top_k or 0), sample_seed=rnd)
+            ro.close()
+        elif a.device_rollouts and a.env == "chess":
+            ro = chess_rollouts()
             raw, summary = ro.text_env_eval(a.n_rollouts, seed_generator=iter(range(rnd * 10 ** 6, 10 ** 9)), temperature=a.policy_temperature or 1.0,
                                             top_k=int(a.policy_top_k or 0), sample_seed=rnd)
             ro.close()
@@ -420,7 +432,7 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--model", default="random:tiny", help="checkpoint directory (reference layout or HF PyTorch) or random:<tiny|small>")
         p.add_argument("--vocab-file", default="wordle_official_400.txt")
         p.add_argument("--out", default=None)
-        p.add_argument("--device-rollouts", type=int, default=0, help="1 = run the Wordle rollouts (bc-eval, ilql evaluation, ppo data collection) on the device-resident engine")
+        p.add_argument("--device-rollouts", type=int, default=0, help="1 = run the rollouts (bc-eval, ilql evaluation, ppo data collection: Wordle, Maze, chess) on the device-resident engine")
         p.add_argument("--rollout-lanes", type=int, default=1, help="device rollouts: independent episode batches in flight at once "
                                                                      "(WordleRolloutEngine.text_env_eval(concurrent=n); >= 4 batches use the graph path)")
         _add(p, defaults)

@@ -103,6 +103,81 @@ int lmrl_wordle_export_state(const void *state_d, uint8_t *trits_d /* [N][26][5]
                              uint32_t *n_filtered_d, uint32_t *n_actions_d, int n, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scripted Wordle policies and the device-resident episode loop — replaces RandomMixturePolicy, OptimalPolicy (with an
+ * optional StartWordPolicy on the first turn) and MixturePolicy (wordle/env/scripted_policies.py:42-153) and the
+ * interact_environment loop of PolicyDataGenerator (wordle/env/data.py:9-34) for N episodes in lock-step.
+ *
+ * Every episode has two MT19937 streams: the ENV stream (random.Random(env_seed): the env's targets and, as in
+ * wordle/misc/data_gen.py where policy and env share one Vocabulary, the words RandomMixturePolicy draws) and the POLICY
+ * stream (random.Random(policy_seed), standing for the module-level generator: the mixture coins and every random.choice of
+ * OptimalPolicy / StartWordPolicy).  OptimalPolicy is the reference policy with an empty cache at the start of every episode.
+ * ------------------------------------------------------------------------------------------ */
+#define LMRL_WORDLE_POLICY_MIXTURE 0 /* RandomMixturePolicy(prob_smart) */
+#define LMRL_WORDLE_POLICY_OPTIMAL 1 /* OptimalPolicy, n_start > 0: StartWordPolicy(start words) answers the first turn */
+#define LMRL_WORDLE_MAX_START_WORDS 64
+typedef struct {
+    int32_t kind;       /* LMRL_WORDLE_POLICY_* */
+    int32_t n_start;    /* OPTIMAL: number of start words (0 = no start-word policy) */
+    int32_t start_off;  /* first start word in start_words[] */
+    int32_t pad_;
+    double prob_smart;  /* MIXTURE */
+} lmrl_wordle_policy_leaf;
+typedef struct {
+    int32_t coin;       /* 1: MixturePolicy(prob1, leaf[0], leaf[1]); 0: leaf[0] alone */
+    int32_t pad_;
+    double prob1;
+    lmrl_wordle_policy_leaf leaf[2];
+    uint32_t start_words[LMRL_WORDLE_MAX_START_WORDS]; /* packed; need not be vocabulary words */
+} lmrl_wordle_policy_desc;
+
+/* Caller-owned scratch for n envs on a V-word list (filtered lists, info gains, the work-item scan).  ZERO it once after
+ * allocation: it also caches the scores of the all-POSSIBLE state, which are the same for every env and every later call on
+ * the same ctx / logtab, so that first-turn sweep (V^2 pattern evaluations) runs once per scratch buffer. */
+size_t lmrl_wordle_policy_scratch_bytes(int n, int n_words);
+/*
+ * One policy.act for every env with active_d[i] != 0 (NULL = all).  Reads the knowledge masks and n_actions of state_d (n_filtered
+ * is recomputed, so a state rebuilt from text needs those 11 rows only).
+ *   logtab_d   double[V + 1], logtab[k] = math.log(k) as the HOST computes it (k >= 1; entry 0 unused) — no device log
+ *   guess_d    packed guesses, the layout lmrl_wordle_step takes; inactive envs untouched
+ *   diag_*     optional (NULL): per env that computed an OptimalPolicy turn, F, len(best_words) and best_info; 0 elsewhere
+ */
+int lmrl_wordle_policy_act(lmrl_wordle_ctx *ctx, const lmrl_wordle_policy_desc *desc, const void *state_d, void *mt_env_d,
+                           void *mt_policy_d, const uint8_t *active_d, const double *logtab_d, void *scratch_d,
+                           size_t scratch_bytes, uint32_t *guess_d, uint32_t *diag_f_d, uint32_t *diag_nbest_d,
+                           double *diag_info_d, int n, void *stream);
+/*
+ * n whole episodes without a host round trip: reset (both streams seeded), then up to 6 x (act, step) with per-env done masking.
+ * Records, [6][n] each, rows of turns an env did not play keep guess = LMRL_WORDLE_BAD_GUESS, obs = 0, reward = 0, flags = 0:
+ *   rec_guess_d / rec_obs_d / rec_reward_d / rec_flags_d   what lmrl_wordle_policy_act chose and lmrl_wordle_step returned
+ *   n_turns_d[n]                                           turns played
+ * active_d is a uint8[n] work buffer.  All launches go to `stream` (graph-capturable after one warm call).
+ */
+int lmrl_wordle_policy_episodes(lmrl_wordle_ctx *ctx, const lmrl_wordle_policy_desc *desc, void *state_d, void *mt_env_d,
+                                void *mt_policy_d, const uint64_t *env_seeds_d, const uint64_t *policy_seeds_d,
+                                const double *logtab_d, void *scratch_d, size_t scratch_bytes, uint8_t *active_d,
+                                uint32_t *rec_guess_d, uint32_t *rec_obs_d, float *rec_reward_d, uint8_t *rec_flags_d,
+                                int32_t *n_turns_d, int n, void *stream);
+/* Host faces of csrc/wordle_policy_core.h (no device): the functions the kernels run, for the CPU test tier.
+ *   words: uint32[V] packed vocabulary in file order; masks10: forb[5] then must[5]; mt: uint32[625] host stream (n = 1 layout) */
+void lmrl_wordle_policy_host_seed(uint32_t *mt, uint64_t seed);
+double lmrl_wordle_policy_host_random(uint32_t *mt);
+uint32_t lmrl_wordle_policy_host_randbelow(uint32_t *mt, uint32_t n);
+/* transition_from_str for one action (obs code as lmrl_wordle_step writes it); LMRL_ERR_ARG if it does not hold 5 symbols */
+int lmrl_wordle_policy_host_apply_feedback(uint32_t *masks10, uint32_t guess, uint32_t obs_code);
+/* filtered list (indices into words) -> returns F */
+int lmrl_wordle_policy_host_filtered(const uint32_t *words, int n_words, const uint32_t *masks10, int32_t *idx_out);
+/* info gain of every stride-th word of the filtered list (gains_out[k], k % stride == 0); literal != 0: by the reference's literal
+ * definition (next states compared as states, sizes counted over the whole vocabulary) instead of the pattern buckets. Returns F. */
+int lmrl_wordle_policy_host_gains(const uint32_t *words, int n_words, const uint32_t *masks10, const double *logtab, int stride,
+                                  int literal, double *gains_out, int32_t *idx_out);
+/* one policy.act on host streams; best_idx_out (int32[V], nullable) receives best_words as vocabulary indices. *n_best_out = 0 when
+ * no OptimalPolicy turn was computed.  Returns the packed guess. */
+uint32_t lmrl_wordle_policy_host_act(const lmrl_wordle_policy_desc *desc, const uint32_t *words, int n_words,
+                                     const uint32_t *masks10, int n_actions, const double *logtab, uint32_t *mt_env,
+                                     uint32_t *mt_policy, int32_t *f_out, int32_t *n_best_out, int32_t *best_idx_out,
+                                     double *best_info_out);
+
+/* ------------------------------------------------------------------------------------------
  * Batched Maze MDP — replaces MazeEnv.reset/step, update_position and the reward functions
  * (maze/env/env.py:104-131,161-214).  Text rendering of observations stays on the host.
  *

@@ -31,6 +31,17 @@ _SIGS = {
     "lmrl_wordle_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lmrl_wordle_set_variant": (c_int, [c_void_p, c_int]),
     "lmrl_wordle_export_state": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_wordle_policy_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "lmrl_wordle_policy_act": (c_int, [c_void_p] * 8 + [c_size_t] + [c_void_p] * 4 + [c_int, c_void_p]),
+    "lmrl_wordle_policy_episodes": (c_int, [c_void_p] * 9 + [c_size_t] + [c_void_p] * 6 + [c_int, c_void_p]),
+    "lmrl_wordle_policy_host_seed": (None, [c_void_p, ctypes.c_uint64]),
+    "lmrl_wordle_policy_host_random": (ctypes.c_double, [c_void_p]),
+    "lmrl_wordle_policy_host_randbelow": (ctypes.c_uint32, [c_void_p, ctypes.c_uint32]),
+    "lmrl_wordle_policy_host_apply_feedback": (c_int, [c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
+    "lmrl_wordle_policy_host_filtered": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "lmrl_wordle_policy_host_gains": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "lmrl_wordle_policy_host_act": (ctypes.c_uint32, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p]),
     "lmrl_maze_create": (c_void_p, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "lmrl_maze_destroy": (None, [c_void_p]),
     "lmrl_maze_state_bytes": (c_size_t, [c_int]),

@@ -162,4 +162,11 @@ LMRL_HD uint32_t mt_randbelow(const MtRef &r, uint32_t n) {
     return v;
 }
 
+// random.Random.random(): genrand_res53, (a >> 5, b >> 6) -> (a * 2^26 + b) / 2^53 (exact in double).
+LMRL_HD double mt_random(const MtRef &r) {
+    const uint32_t a = mt_next(r) >> 5;
+    const uint32_t b = mt_next(r) >> 6;
+    return ((double)a * 67108864.0 + (double)b) * (1.0 / 9007199254740992.0);
+}
+
 }  // namespace lmrl

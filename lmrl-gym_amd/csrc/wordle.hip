@@ -16,20 +16,9 @@
 #include "common.h"
 #include "mt19937.h"
 #include "wordle_core.h"
+#include "wordle_ctx.h"
 
 namespace lmrl {
-
-struct WordleCtx {
-    uint32_t *words_d = nullptr;   // [V] packed 5x5-bit letters, file order
-    uint32_t *wmask_d = nullptr;   // [V] 26-bit letter-presence masks
-    int V = 0;
-    int require = 1;
-    float bad_reward = -1.f;
-    int step_variant = 0;          // 0: by batch size, 1: one wave per env, 2: one lane per env (lmrl_wordle_set_variant)
-};
-
-// rows of the SoA game-state buffer
-enum { ROW_FORB = 0, ROW_MUST = 5, ROW_NFILT = 10, ROW_NACT = 11, ROW_HIST = 12 };
 
 __global__ __launch_bounds__(kMtSeedLanes) void wordle_reset_kernel(uint32_t *st, void *mt, const uint64_t *seeds, const uint8_t *mask,
                                                                     const uint32_t *table, int V, int n) {
@@ -260,8 +249,6 @@ int mt_table(const uint32_t **out);  // mt19937.hip
 }  // namespace lmrl
 
 using namespace lmrl;
-
-struct lmrl_wordle_ctx : public WordleCtx {};
 
 extern "C" {
 

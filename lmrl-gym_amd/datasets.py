@@ -232,3 +232,27 @@ def generate_wordle_dataset(vocab, n_data: int, prob_smart: float, seed: int = 0
         items += [text_trajectory_to_item(hist[i], rews[i], True) for i in range(n)]
     env.close()
     return (items, all_seeds) if return_seeds else items
+
+
+def generate_wordle_dataset_device(vocab, n_data: int, policy, seed: int = 0, bsize: int = 1024, require_words_in_vocab: bool = True,
+                                   bad_word_reward: float = -1.0, return_seeds: bool = False):
+    """`n_data` episodes of a scripted policy (`envs.wordle_policies`: RandomMixturePolicy, OptimalPolicy, MixturePolicy) with policy,
+    env and episode loop on the device (`WordleScriptedRollouts`), `bsize` episodes per launch sequence; returns jsonl items in the
+    format of `generate_wordle_dataset`.  Env seeds follow `PolicyDataGenerator` (`random.Random(seed).randint(0, 2**31 - 1)`,
+    wordle/env/data.py:27), and the words are the reference policies' own, draw for draw, on those seeds."""
+    from .envs import wordle as W
+    from .envs.wordle_policies import PolicyDataGenerator
+    env = W.WordleEnvironment(vocab, require_words_in_vocab, bad_word_reward)
+    gen = PolicyDataGenerator(env, policy, seed=seed, bsize=min(bsize, max(n_data, 1)))
+    items: List[Dict[str, Any]] = []
+    env_seeds: List[int] = []
+    pol_seeds: List[int] = []
+    try:
+        while len(items) < n_data:
+            rec = gen.next_records(min(bsize, n_data - len(items)))
+            items += rec.to_items()
+            env_seeds += [int(s) for s in rec.env_seeds]
+            pol_seeds += [int(s) for s in rec.policy_seeds]
+    finally:
+        gen.close()
+    return (items, env_seeds, pol_seeds) if return_seeds else items

@@ -7,6 +7,8 @@
     python scripts/harness.py bc-eval                                                # llm_rl_scripts/wordle/bc/eval_bc_gpt2.py
     python scripts/harness.py maze-eval                                              # llm_rl_scripts/maze/bc/fully_observed_bc.py (eval part)
     python scripts/harness.py gen-data --n-data 1000 --out d.jsonl                   # llm_rl_scripts/wordle/misc/data_gen.py
+    python scripts/harness.py gen-data --policy optimal --start-word raise --device-loop 1 --out d.jsonl   # scripted policies + loop on the device
+    python scripts/harness.py optimal-perf --n 1000                                  # llm_rl_scripts/wordle/misc/optimal_perf.py
 
 Hyper-parameter names and defaults are the reference scripts' own.  Not carried over: tyro, wandb, GCS, mesh-shape flags (one
 process per GPU + `torch.distributed.run` instead).  `--model` is a checkpoint directory in the reference layout
@@ -109,11 +111,44 @@ def _log(tag, obj):
 
 
 # --------------------------------------------------------------------------------------------------------------- commands
+def _scripted_policy(a, vocab):
+    """--policy mixture | optimal | optimal-mixture (a --mix-prob coin between the two) with --start-word w1,w2 | default | none."""
+    from lmrl_gym_amd.envs import wordle_policies as P
+    sw = getattr(a, "start_word", "none")
+    start = None if sw == "none" else P.StartWordPolicy(None if sw == "default" else sw.split(","))
+    mixture, optimal = P.RandomMixturePolicy(a.prob_smart, vocab), P.OptimalPolicy(vocab, start)
+    return dict(mixture=mixture, optimal=optimal)[a.policy] if a.policy != "optimal-mixture" else P.MixturePolicy(a.mix_prob, optimal, mixture)
+
+
 def cmd_gen_data(a):
     from lmrl_gym_amd import datasets as DS
     vocab, _ = _wordle_env(a)
-    n = DS.write_jsonl(a.out, DS.generate_wordle_dataset(vocab, a.n_data, a.prob_smart, seed=a.seed))
-    _log("gen_data", dict(items=n, path=a.out))
+    if a.device_loop:
+        items = DS.generate_wordle_dataset_device(vocab, a.n_data, _scripted_policy(a, vocab), seed=a.seed, bsize=a.bsize)
+    elif a.policy != "mixture":
+        raise SystemExit("gen-data: --policy optimal / optimal-mixture run on the device loop (--device-loop 1)")
+    else:
+        items = DS.generate_wordle_dataset(vocab, a.n_data, a.prob_smart, seed=a.seed)
+    _log("gen_data", dict(items=DS.write_jsonl(a.out, items), path=a.out, policy=a.policy, device_loop=a.device_loop))
+
+
+def cmd_optimal_perf(a):
+    """Mean reward of optimal play (wordle/misc/optimal_perf.py: OptimalPolicy behind a start word, text_env_eval's summary)."""
+    import random
+    from lmrl_gym_amd.envs import wordle_policies as P
+    vocab, _ = _wordle_env(a)
+    a.policy, a.prob_smart = "optimal", 0.0
+    loop = P.WordleScriptedRollouts(vocab, _scripted_policy(a, vocab), min(a.bsize, a.n))
+    rng = random.Random(a.seed)
+    recs = []
+    for b0 in range(0, a.n, loop.n):
+        k = min(loop.n, a.n - b0)
+        recs.append(loop.run([rng.randint(0, 2 ** 31 - 1) for _ in range(k)], [rng.randint(0, 2 ** 31 - 1) for _ in range(k)]))
+    loop.close()
+    rewards = np.concatenate([r.reward.sum(axis=0) for r in recs])
+    lengths = np.concatenate([r.n_turns for r in recs])
+    _log("optimal_perf", dict(n=int(len(rewards)), reward_mean=float(rewards.mean()), reward_std=float(rewards.std()),
+                              length_mean=float(lengths.mean()), solved=float((rewards > -6).mean())))
 
 
 def cmd_ilql(a):
@@ -463,6 +498,15 @@ def build_parser() -> argparse.ArgumentParser:
     g.set_defaults(fn=cmd_gen_data)
     g.add_argument("--n-data", type=int, default=1000); g.add_argument("--prob-smart", type=float, default=0.5)
     g.add_argument("--seed", type=int, default=0); g.add_argument("--out", required=True); g.add_argument("--vocab-file", default="wordle_official_400.txt")
+    o = sub.add_parser("optimal-perf")
+    o.set_defaults(fn=cmd_optimal_perf)
+    o.add_argument("--n", type=int, default=1000); o.add_argument("--seed", type=int, default=0); o.add_argument("--vocab-file", default="wordle_official_400.txt")
+    g.add_argument("--policy", default="mixture", choices=["mixture", "optimal", "optimal-mixture"])
+    g.add_argument("--mix-prob", type=float, default=0.5, help="optimal-mixture: probability of the optimal policy per turn")
+    g.add_argument("--device-loop", type=int, default=0, help="1 = policy, env and episode loop on the device (generate_wordle_dataset_device)")
+    for p in (g, o):
+        p.add_argument("--start-word", default="raise" if p is o else "none", help="first-turn words of OptimalPolicy: w1,w2,... | default | none")
+        p.add_argument("--bsize", type=int, default=1024)
     return ap
 
 

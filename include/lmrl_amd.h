@@ -709,6 +709,50 @@ int lmrl_wordle_tok_steer(lmrl_wordle_tok_ctx *c, const uint32_t *scripted_guess
                           void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rollout records -> the blocked ILQL / MC / BC datasets without leaving the device (csrc/offline_data.hip, csrc/offline_data_core.h).
+ * Replaces the jsonl round trip of the offline trainers: data_gen.py:53-62 -> train_ilql_gpt2.py:123-152 (re-tokenisation,
+ * ILQLData / MCData.from_token_trajectory_chain, ilql/data.py:18-79, mc_returns/data.py:21-74, block_sequences) and the
+ * (ids, training mask) pairs of the BC scripts.
+ * ------------------------------------------------------------------------------------------ */
+/* The first n episodes of lmrl_wordle_policy_episodes' records (guess / obs / reward / flags [6][stride], n_turns [stride]) as lmrl_ppo_records
+ * rows of pitch cap: the canonical ids of the REFORMATTED history ('Wordle:\n', 'a b c d e\n', 'g y b b y\n' or '\n'; env.py:7-17), is_action per
+ * text, a turn's reward on the '\n' that closes its action, 0 on the header and the observations (TokenTrajectory.from_text_trajectory,
+ * environment.py:349-380); slots past an episode's last token hold pad / 0 / 0.  done_d[e] = bit 0 of the last played turn's flags.
+ * cap >= n_header + 72 holds every episode.  err_d (optional, one int32): episodes whose policy ran out of words (flag bit 3) or that do not
+ * fit cap.  One wave per episode, lanes over token slots. */
+int lmrl_wordle_tok_scripted_records(const lmrl_wordle_tokens *tokens, const uint32_t *guess_d, const uint32_t *obs_d, const float *reward_d,
+                                     const uint8_t *flags_d, const int32_t *n_turns_d, int stride, int n, int cap, int32_t *tokens_d,
+                                     uint8_t *is_action_d, float *rec_reward_d, int32_t *n_tok_d, uint8_t *done_d, int32_t *err_d, void *stream);
+/* The same rule on ONE episode in host memory (guess6 / obs6 / reward6 / flags6: its six turns; CPU-tier tests, no GPU needed): fills
+ * tokens_out / is_action_out / reward_out [cap], *done_out, returns the number of tokens (-1: bad argument, or the episode does not fit cap). */
+int lmrl_wordle_host_scripted_record(const lmrl_wordle_tokens *tokens, const uint32_t *guess6, const uint32_t *obs6, const float *reward6,
+                                     const uint8_t *flags6, int n_turns, int cap, int32_t *tokens_out, uint8_t *is_action_out, float *reward_out,
+                                     int *done_out);
+/* Outputs of lmrl_offline_block for m rows of width T = max_len; NULL = not wanted (input_ids and lengths are required). */
+typedef struct {
+    int32_t *input_ids;          /* [m][T]      tokens, padded with the pad id */
+    uint8_t *should_take_action; /* [m][T - 1]  is_action[1:] */
+    float *rewards;              /* [m][T - 1]  reward[1:] */
+    float *returns;              /* [m][T - 1]  returns_d rows (MC reward-to-go already scattered to positions), blocked like rewards */
+    float *training_mask;        /* [m][T]      float(is_action) per token: the segment weights of MaskDataset */
+    uint8_t *dones;              /* [m]         the trajectory's own done: the chain's done on its last trajectory, 0 before */
+    int32_t *lengths;            /* [m]         min(n_tok, T) */
+    int32_t *next_token_ids;     /* [m][T]      multi-trajectory chains: the next trajectory's tokens up to (excluding) its first action at
+                                                index >= 1, or all of it when it has none (ilql/data.py:62-71) */
+    uint8_t *next_dones;         /* [m]         0 in the first case, the next trajectory's done in the second */
+    int32_t *next_lengths;       /* [m] */
+} lmrl_offline_blocks;
+/* block_sequences(Padding.RIGHT, Truncation.RIGHT | LEFT (truncate_left != 0), max_len) of the rows keep_d[0 .. n_keep) of the records (keep_d NULL:
+ * all n rows).  The [T - 1] arrays are x[1:] blocked with max_len - 1 ON THEIR OWN, as ILQLData.block / MCData.block do.  returns_d
+ * [n][returns_pitch]: per source row the un-truncated reward-to-go on the shifted grid (lmrl_rtg over reward[1:] / is_action[1:]), required with
+ * out->returns.  A chain's last trajectory has no next trajectory (None in the reference): its next_token_ids row is all padding, next_dones 1. */
+int lmrl_offline_block(const lmrl_ppo_records *rec, const int32_t *keep_d, int n_keep, int max_len, int pad, int truncate_left, const float *returns_d,
+                       int returns_pitch, const lmrl_offline_blocks *out, void *stream);
+/* returns_d [n_chains] = the undiscounted sum of every reward of a chain (the score of bc/data.py:32-47's filter): summed in double in a fixed
+ * order, rounded to float32 once.  The trajectories of a chain are consecutive rows. */
+int lmrl_record_returns(const lmrl_ppo_records *rec, float *returns_d, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device token <-> game bookkeeping for lock-step Maze rollouts (csrc/maze_tokens.hip), for histories of one item
  * (last_k = 1, the reference's Maze harness: maze/bc/fully_observed_bc.py:230-237): a turn's prompt is the observation of the current
  * cell, a pure function of (goal, cell) (maze/env/env.py:8-81), so prompts come from a token table instead of the host tokenizer, and the

@@ -151,6 +151,10 @@ _SIGS = {
     "lmrl_wordle_tok_guess": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lmrl_wordle_tok_observe": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lmrl_wordle_tok_steer": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "lmrl_wordle_tok_scripted_records": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int] + [c_void_p] * 7),
+    "lmrl_wordle_host_scripted_record": (c_int, [c_void_p] * 5 + [c_int, c_int] + [c_void_p] * 4),
+    "lmrl_offline_block": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "lmrl_record_returns": (c_int, [c_void_p, c_void_p, c_void_p]),
     "lmrl_prof_enable": (None, [ctypes.c_uint]),
     "lmrl_prof_reset": (None, []),
     "lmrl_prof_n_tags": (c_int, []),

@@ -43,19 +43,38 @@ def masked_ce_forward_backward(m: GPT2F32, ids: np.ndarray, am: np.ndarray, pos:
     """loss = sum(w * CE(logits[:, :-1], ids[:, 1:])) / denom with the masked sums all-reduced across ranks; when `grads`
     is given, grad_scale * d loss / d params is ACCUMULATED into it (shared by the BC trainer and the PPO BC term)."""
     import torch
+    from .ppo import _on_device
+    on_dev = _on_device(ids)
     B, T = ids.shape
     R, dev = B * T, m.dev
     ids_d = _t(ids, np.int32)
     hid, cache = m.forward(ids_d, _t(am, np.uint8), _t(pos, np.int32))
     if D.is_distributed():
         denom = float(D.allreduce_sum_(torch.tensor([denom], dtype=torch.float64, device=dev)).item())
-    wn = np.asarray(w, dtype=np.float32) / np.float32(denom)                     # [B, T-1] CE weights
-    # the LM head runs on the rows with a non-zero weight only (with non_action_weight = 0: the action tokens) — rows of weight 0
-    # contribute exact zeros to the loss and to every gradient
-    rows_h = masked_rows(wn != 0, T)
-    Ra = int(rows_h.size)
+    if on_dev:
+        # device batch: `w` is (attention_mask[:, 1:], is_action[:, 1:], non_action_weight).  A weight is 0, 1 or non_action_weight, so w / denom
+        # takes three values: the two quotients are formed on the host in float32 exactly as the numpy path divides, and selected per token on
+        # the device — no device division, same bits
+        from .ppo_device import masked_rows_device
+        am1, ia1, naw = w
+        c_act, c_non = np.float32(1.0) / np.float32(denom), np.float32(naw) / np.float32(denom)
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        wn_d = torch.where(am1 != 0, torch.where(ia1 != 0, zero + float(c_act), zero + float(c_non)), zero).contiguous()
+        wfull_d = torch.zeros((B, T), dtype=torch.float32, device=dev)
+        wfull_d[:, :-1] = wn_d
+        idx_dev, tgt_dev, Ra = masked_rows_device((wn_d != 0).to(torch.uint8).contiguous(), None, ids_d, T)
+    else:
+        wn = np.asarray(w, dtype=np.float32) / np.float32(denom)                     # [B, T-1] CE weights
+        # the LM head runs on the rows with a non-zero weight only (with non_action_weight = 0: the action tokens) — rows of weight 0
+        # contribute exact zeros to the loss and to every gradient
+        rows_h = masked_rows(wn != 0, T)
+        Ra = int(rows_h.size)
     compact = compact_rows and 0 < Ra < R
-    if compact:
+    if compact and on_dev:
+        idx, tgt = idx_dev, tgt_dev
+        hq, Rq = ops.gather_rows(hid, idx, Ra, m.d), Ra
+        coef = ops.gather_rows(wfull_d.view(R, 1), idx, Ra, 1).view(Ra)
+    elif compact:
         idx = _t(rows_h, np.int32)
         hq, Rq = ops.gather_rows(hid, idx, Ra, m.d), Ra
         tgt = _t(ids[:, 1:][wn != 0].astype(np.int32), np.int32)
@@ -64,9 +83,12 @@ def masked_ce_forward_backward(m: GPT2F32, ids: np.ndarray, am: np.ndarray, pos:
         hq, Rq = hid, R
         tgt = torch.zeros(R, dtype=torch.int32, device=dev)
         tgt.view(B, T)[:, :-1] = ids_d[:, 1:]
-        wfull = np.zeros((B, T), dtype=np.float32)
-        wfull[:, :-1] = wn
-        coef = _t(wfull.reshape(-1), np.float32)
+        if on_dev:
+            coef = wfull_d.reshape(-1).clone()
+        else:
+            wfull = np.zeros((B, T), dtype=np.float32)
+            wfull[:, :-1] = wn
+            coef = _t(wfull.reshape(-1), np.float32)
     logits, logits_b, lse, lp = m.lm_ce(hq, Rq, tgt)
     # loss = sum(coef * CE) = -sum(coef * logprob): a dot product done as a 1 x 1 x R GEMM on the matrix core
     out = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -100,9 +122,19 @@ class GPT2BCTrain:
         self.last_grads = None
 
     def step(self, input_ids, is_action, attention_mask=None, position_ids=None, train: bool = True):
-        ids = np.asarray(input_ids, dtype=np.int32)
-        am, pos = initialize_attn_mask_pos_ids(ids, self.pad, attention_mask, position_ids)
-        w, denom = bc_weights(am, is_action, self.w)
+        import torch
+        from .ppo import _on_device
+        if _on_device(input_ids):
+            # a batch that never left the device (`offline_device.DeviceMaskDataset.batch`); one integer comes back: the normaliser sum(attn[:, 1:])
+            from .mc_returns import _device_masks
+            ids = _t(input_ids, np.int32)
+            am, pos = _device_masks(ids, self.pad, attention_mask, position_ids)
+            am1 = am[:, 1:].contiguous()
+            w, denom = (am1, _t(is_action, np.float32)[:, 1:].contiguous(), self.w), float(int(am1.sum(dtype=torch.int64).item()))
+        else:
+            ids = np.asarray(input_ids, dtype=np.int32)
+            am, pos = initialize_attn_mask_pos_ids(ids, self.pad, attention_mask, position_ids)
+            w, denom = bc_weights(am, is_action, self.w)
         grads = self.model.zero_grads() if train else None
         loss = masked_ce_forward_backward(self.model, ids, am, pos, w, denom, grads)
         if not train:

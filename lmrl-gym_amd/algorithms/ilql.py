@@ -17,7 +17,7 @@ from .. import dist as D
 from ..train import ops
 from ..train.gpt2_f32 import AdamW, GPT2F32, MLPHeadF32
 from .common import BlockingStrategy, Padding, Truncation, block_sequences, initialize_attn_mask_pos_ids, stats_from_sums, masked_rows
-from .ppo import _t
+from .ppo import _on_device, _t
 
 
 # ----------------------------------------------------------------------------- data (ilql/data.py:10-132)
@@ -209,14 +209,26 @@ class GPT2ILQLTrain:
     def step(self, input_ids, should_take_action, rewards, dones, next_token_ids=None, next_dones=None, prng_key=None,
              attention_mask=None, position_ids=None, next_tokens_attention_mask=None, next_tokens_position_ids=None, train: bool = True):
         import torch
-        ids = np.asarray(input_ids, dtype=np.int32)
-        am, pos = initialize_attn_mask_pos_ids(ids, self.pad, attention_mask, position_ids)
-        B, T = ids.shape
+        on_dev = _on_device(input_ids)
+        if on_dev:
+            # a batch that never left the device (`offline_device.DeviceILQLDataset.batch`): masks, positions, the Q-head row list and its
+            # targets come from csrc/ppo_data.hip; the host learns one integer (the row count that sizes the head products)
+            from .mc_returns import _device_masks
+            from .ppo_device import masked_rows_device
+            ids_d = _t(input_ids, np.int32)
+            am_d, pos_d = _device_masks(ids_d, self.pad, attention_mask, position_ids)
+            am = am_d
+            B, T = ids_d.shape
+        else:
+            ids = np.asarray(input_ids, dtype=np.int32)
+            am, pos = initialize_attn_mask_pos_ids(ids, self.pad, attention_mask, position_ids)
+            B, T = ids.shape
         R, T1 = B * T, T - 1
         base = self.base
         dev = base.dev
         V = self.q1.dout
-        ids_d, pos_d, am_d = _t(ids, np.int32), _t(pos, np.int32), _t(am, np.uint8)
+        if not on_dev:
+            ids_d, pos_d, am_d = _t(ids, np.int32), _t(pos, np.int32), _t(am, np.uint8)
         hid, cache = base.forward(ids_d, am_d, pos_d)
         thid = self.target_base.forward(ids_d, am_d, pos_d, inference=True)[0] if self.target_base is not None else hid      # never differentiated
         vo, vc = self.v.forward(hid, R)
@@ -227,17 +239,23 @@ class GPT2ILQLTrain:
         tq2sa = self.q2_target.forward_at(thid, R, tgt)
         new = lambda: torch.empty(R, dtype=torch.float32, device=dev)
         sl = lambda x: x.view(B, T)[:, :-1].contiguous()
-        sta = np.asarray(should_take_action, dtype=bool)
+        sta = _t(should_take_action, np.uint8) if on_dev else np.asarray(should_take_action, dtype=bool)
         # rows the Q terms of the loss read: should_take_action (host-known).  The q1 / q2 / v L2 terms and target_q select by
         # should_take_action ALONE (qv_query_indicators / sa_mask, base_interface.py:57-83); only n and the CQL terms also multiply by the
         # attention mask (:48-49, :91-95) — the loss kernel applies that second mask itself, so the compacted row set must be the superset.
         # The Q heads run on those rows only (gathered hidden states -> logits -> lse / gather; backward: dlogits -> head backward ->
         # scatter-add into d_hidden)
         q_mask = sta
-        q_rows = masked_rows(q_mask, T)
-        Ra = int(q_rows.size)
+        if on_dev:
+            idx_dev, tgt_dev, Ra = masked_rows_device(sta, None, ids_d, T)
+        else:
+            q_rows = masked_rows(q_mask, T)
+            Ra = int(q_rows.size)
         compact = self.compact_q_rows and 0 < Ra < R
-        if compact:
+        if compact and on_dev:
+            idx, tgt_q, Rq = idx_dev, tgt_dev, Ra
+            hq = ops.gather_rows(hid, idx, Ra, base.d)
+        elif compact:
             idx = _t(q_rows, np.int32)
             hq = ops.gather_rows(hid, idx, Ra, base.d)
             tgt_q = _t(ids[:, 1:][q_mask].astype(np.int32), np.int32)
@@ -271,8 +289,27 @@ class GPT2ILQLTrain:
             q1sa, q2sa, ce1, ce2 = q1sa_q, q2sa_q, ce1_q, ce2_q
         v_full = vo.view(B, T)
         # v_final (interface.py:253-273)
-        d = np.asarray(dones, dtype=np.float32)
-        if next_token_ids is not None:
+        if on_dev:
+            # dones / next_dones stay where they are; the row of the last attended / last action token is integer arithmetic on [B, T] masks
+            last_one = lambda m: (m.shape[1] - 1) - torch.argmax(torch.flip(m.to(torch.int32), dims=[1]), dim=1)      # np.argmax: the first maximum
+            d_d = _t(dones, np.float32)
+            if next_token_ids is not None:
+                nids_d = _t(next_token_ids, np.int32)
+                nam_d, npos_d = _device_masks(nids_d, self.pad, next_tokens_attention_mask, next_tokens_position_ids)
+                nhid, ncache = base.forward(nids_d, nam_d, npos_d)
+                rows = torch.arange(B, device=dev, dtype=torch.int64) * nids_d.shape[1] + last_one(nam_d)
+                final_h = nhid.index_select(0, rows).contiguous()
+                nv, _ = self.v.forward(final_h, B)
+                v_final = torch.empty(B, dtype=torch.float32, device=dev)
+                ops.axpby(1.0, nv.view(B), 0.0, None, v_final)
+                v_final = v_final * (1.0 - _t(next_dones, np.float32))
+            else:
+                last_action, last_token = last_one(sta) + 1, last_one(am_d)
+                final_idx = torch.where(d_d != 0, last_token, last_action)      # (1 - d) * last_action + d * last_token for d in {0, 1}
+                rows = torch.arange(B, device=dev, dtype=torch.int64) * T + final_idx
+                v_final = vo.view(R).index_select(0, rows) * (1.0 - d_d)
+        elif next_token_ids is not None:
+            d = np.asarray(dones, dtype=np.float32)
             nids = np.asarray(next_token_ids, dtype=np.int32)
             nam, npos = initialize_attn_mask_pos_ids(nids, self.pad, next_tokens_attention_mask, next_tokens_position_ids)
             nhid, ncache = base.forward(_t(nids, np.int32), _t(nam, np.uint8), _t(npos, np.int32))
@@ -284,6 +321,7 @@ class GPT2ILQLTrain:
             ops.axpby(1.0, nv.view(B), 0.0, None, v_final)
             v_final = v_final * _t(1.0 - np.asarray(next_dones, dtype=np.float32), np.float32)   # (1 - next_dones): host-known 0/1 mask
         else:
+            d = np.asarray(dones, dtype=np.float32)
             last_action = (T1 - 1) - np.argmax(np.flip(sta, axis=1).astype(np.int32), axis=1) + 1
             last_token = (T - 1) - np.argmax(np.flip(am, axis=1).astype(np.int32), axis=1)
             final_idx = ((1 - d) * last_action + d * last_token).astype(np.int64)

@@ -110,6 +110,19 @@ def mc_loss(q, q_logits, token_ids, attention_mask, should_take_action, returns,
     return loss, logs
 
 
+def _device_masks(ids_d, pad, attention_mask, position_ids):
+    """`initialize_attn_mask_pos_ids` for device ids: the batch's own masks where it carries them, else `ids != pad` (`lmrl_seq_mask_pos`)."""
+    from .ppo_device import mask_pos_device
+    if attention_mask is not None and position_ids is not None:
+        return _t(attention_mask, np.uint8), _t(position_ids, np.int32)
+    import torch
+    if attention_mask is None:
+        am0, pos0 = mask_pos_device(ids_d, pad)
+        return am0, (_t(position_ids, np.int32) if position_ids is not None else pos0)
+    am_d = _t(attention_mask, np.uint8)      # a given mask without positions: clip(cumsum(mask) - 1, 0), integer arithmetic
+    return am_d, torch.clamp(torch.cumsum(am_d.to(torch.int32), dim=1) - 1, min=0).to(torch.int32).contiguous()
+
+
 class GPT2MCTrain:
     """fp32 MC-returns trainer: GPT-2 base + Q `MLPHead` (d -> d -> V), loss = `mc_loss`
     (LLM_RL/algorithms/mc_returns/gpt2/interface.py:57-170; step signature of mc_returns/base_interface.py:89-137).
@@ -128,22 +141,39 @@ class GPT2MCTrain:
     def step(self, input_ids, should_take_action, returns, prng_key=None, attention_mask=None, position_ids=None, train: bool = True):
         import torch
         from .. import dist as D
-        from .common import initialize_attn_mask_pos_ids
-        ids = np.asarray(input_ids, dtype=np.int32)
-        am, pos = initialize_attn_mask_pos_ids(ids, self.pad, attention_mask, position_ids)
-        B, T = ids.shape
+        from .ppo import _on_device
+        on_dev = _on_device(input_ids)
+        if on_dev:
+            # a batch that never left the device (`offline_device.DeviceMCDataset.batch`): masks, positions, the Q-head row list and its
+            # targets come from csrc/ppo_data.hip; the host learns one integer (the row count that sizes the head products)
+            from .ppo_device import masked_rows_device
+            ids_d = _t(input_ids, np.int32)
+            am, pos = _device_masks(ids_d, self.pad, attention_mask, position_ids)
+            B, T = ids_d.shape
+        else:
+            from .common import initialize_attn_mask_pos_ids
+            ids = np.asarray(input_ids, dtype=np.int32)
+            am, pos = initialize_attn_mask_pos_ids(ids, self.pad, attention_mask, position_ids)
+            B, T = ids.shape
         R, base, dev, V = B * T, self.base, self.base.dev, self.q_head.dout
-        ids_d = _t(ids, np.int32)
+        if not on_dev:
+            ids_d = _t(ids, np.int32)
         hid, cache = base.forward(ids_d, _t(am, np.uint8), _t(pos, np.int32))
         # the Q head runs on the rows the loss reads: should_take_action (the L2 term selects by it alone — q_query_indicators / a_mask,
         # mc_returns/base_interface.py:32-41; the CQL term and n also multiply by the attention mask, which the loss kernel applies) — see
         # GPT2ILQLTrain.compact_q_rows
         from .common import masked_rows
-        q_mask = np.asarray(should_take_action, dtype=bool)
-        rows_h = masked_rows(q_mask, T)
-        Ra = int(rows_h.size)
+        if on_dev:
+            idx_dev, tgt_dev, Ra = masked_rows_device(_t(should_take_action, np.uint8), None, ids_d, T)
+        else:
+            q_mask = np.asarray(should_take_action, dtype=bool)
+            rows_h = masked_rows(q_mask, T)
+            Ra = int(rows_h.size)
         compact = self.compact_q_rows and 0 < Ra < R
-        if compact:
+        if compact and on_dev:
+            idx, tgt = idx_dev, tgt_dev
+            hq, Rq = ops.gather_rows(hid, idx, Ra, base.d), Ra
+        elif compact:
             idx = _t(rows_h, np.int32)
             hq, Rq, tgt = ops.gather_rows(hid, idx, Ra, base.d), Ra, _t(ids[:, 1:][q_mask].astype(np.int32), np.int32)
         else:

@@ -256,3 +256,43 @@ def generate_wordle_dataset_device(vocab, n_data: int, policy, seed: int = 0, bs
     finally:
         gen.close()
     return (items, env_seeds, pol_seeds) if return_seeds else items
+
+
+def wordle_offline_dataset_device(vocab, n_data: int, policy, tokens=None, kind: str = "ilql", seed: int = 0, bsize: int = 1024,
+                                  max_length: Optional[int] = 512, truncation=None, gamma: float = 0.99, require_words_in_vocab: bool = True,
+                                  bad_word_reward: float = -1.0):
+    """The episodes of `generate_wordle_dataset_device` (same policy, same seeds, same order) as ONE device-resident blocked dataset:
+    `bsize` episodes per launch sequence on `WordleScriptedRollouts`, their records tokenised where they lie (`token_records`) and blocked by
+    `algorithms.offline_device` — no jsonl item, host tokenizer or numpy blocking in between.  kind: "ilql" -> `DeviceILQLDataset`,
+    "mc" -> `DeviceMCDataset` (reward-to-go with `gamma`), "bc" -> `DeviceMaskDataset`.  tokens: a `rollout.WordleTokenTable` (default GPT-2
+    ids; its pad id pads the rows).  truncation: `Truncation.RIGHT` (default; the ILQL / MC scripts) or `Truncation.LEFT` (the BC scripts)."""
+    import random
+    from .algorithms import offline_device as OD
+    from .algorithms.common import BlockingStrategy, Padding, Truncation
+    from .envs.wordle_policies import WordleScriptedRollouts
+    from .rollout import WordleTokenTable
+    if kind not in ("ilql", "mc", "bc"):
+        raise ValueError(f"kind must be 'ilql', 'mc' or 'bc', not {kind!r}")
+    tokens = tokens or WordleTokenTable.default_gpt2()
+    bs = BlockingStrategy(Padding.RIGHT, truncation or Truncation.RIGHT, max_length if max_length is not None else len(tokens.header) + 72)
+    rng, policy_rng = random.Random(seed), random.Random(None if seed is None else seed + 1)      # PolicyDataGenerator's two sequences
+    loop = WordleScriptedRollouts(vocab, policy, min(bsize, max(n_data, 1)), require_words_in_vocab, bad_word_reward)
+    parts, done = [], 0
+    try:
+        while done < n_data:
+            n = min(loop.n, n_data - done)
+            env_seeds = [rng.randint(0, 2 ** 31 - 1) for _ in range(n)]
+            pol_seeds = [policy_rng.randint(0, 2 ** 31 - 1) for _ in range(n)]
+            pad = loop.n - n
+            loop.run_device(env_seeds + [env_seeds[-1]] * pad, pol_seeds + [pol_seeds[-1]] * pad)
+            rec = loop.token_records(n, tokens=tokens)
+            if kind == "ilql":
+                parts.append(OD.ilql_data_from_records(rec, bs, tokens.pad))
+            elif kind == "mc":
+                parts.append(OD.mc_data_from_records(rec, gamma, bs, tokens.pad))
+            else:
+                parts.append(OD.mask_data_from_records(rec, bs, tokens.pad))
+            done += n
+    finally:
+        loop.close()
+    return type(parts[0]).concat(parts)

@@ -419,6 +419,32 @@ class WordleScriptedRollouts:
             raise IndexError("Cannot choose from an empty sequence (filtered vocabulary is empty)")
         return rec
 
+    def token_records(self, n: Optional[int] = None, tokens=None, cap: Optional[int] = None):
+        """The first `n` episodes of the last `run_device` as `algorithms.ppo_device.PPORecords` (`lmrl_wordle_tok_scripted_records`): the rows
+        `to_items()` followed by the tokenizer would give (reformatted history, reward on the newline closing each action), built from the
+        resident record buffers; no token data visits the host.  tokens: a `rollout.WordleTokenTable` (default: GPT-2 ids); cap: row pitch
+        (default: the longest possible episode).  One 4-byte readback reports episodes whose policy ran out of words, as `records()` does."""
+        import torch as t
+        from ..algorithms.ppo_device import PPORecords
+        from ..rollout import WordleTokenTable
+        tokens = tokens or WordleTokenTable.default_gpt2()
+        n = self.n if n is None else int(n)
+        assert 0 < n <= self.n
+        cap = len(tokens.header) + W.N_TRIES * 12 if cap is None else int(cap)
+        tok = t.empty((n, cap), dtype=t.int32, device=self.dev)
+        ia = t.empty((n, cap), dtype=t.uint8, device=self.dev)
+        rw = t.empty((n, cap), dtype=t.float32, device=self.dev)
+        n_tok, done = t.empty(n, dtype=t.int32, device=self.dev), t.empty(n, dtype=t.uint8, device=self.dev)
+        err = t.empty(1, dtype=t.int32, device=self.dev)
+        ct = tokens.c_struct()
+        p = _lib.ptr
+        _lib.check(self._L.lmrl_wordle_tok_scripted_records(ctypes.byref(ct), p(self.guess), p(self.obs), p(self.reward), p(self.flags), p(self.n_turns),
+                                                            self.n, n, cap, p(tok), p(ia), p(rw), p(n_tok), p(done), p(err), _lib.stream_ptr()),
+                   "lmrl_wordle_tok_scripted_records")
+        if int(err.cpu().numpy()[0]):
+            raise IndexError("Cannot choose from an empty sequence (filtered vocabulary is empty), or an episode does not fit the row pitch")
+        return PPORecords(tok, ia, rw, n_tok, done)
+
     def run(self, env_seeds, policy_seeds, use_graph: bool = False) -> ScriptedRecords:
         """Fewer seeds than bsize: the batch is padded with repeats of the last episode and the records cut back."""
         env_seeds, policy_seeds = list(env_seeds), list(policy_seeds)

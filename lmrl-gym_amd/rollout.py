@@ -455,6 +455,42 @@ class WordleRolloutEngine:
             timings["rollout_ms"] = timings.get("rollout_ms", 0.0) + t_roll
         return ds, (kls[0] if len(kls) == 1 else torch.cat(kls)), summary
 
+    def record_rollouts(self, n_rollouts: int, seed_generator=None, temperature: float = 1.0, sample_seed: int = 0, use_graph: Optional[bool] = None,
+                        top_k: int = 0, top_p: float = 0.0):
+        """`text_env_eval(n_rollouts, bsize=B)` that keeps the episodes where they are -> (PPORecords of all n_rollouts episodes, summary).  Seeds,
+        sampler keys and the eager / graph choice are those of `text_env_eval` on one lane, so the same call history gives the same episodes; per
+        episode batch the first n_k rows of the record are copied device to device (the engine's buffers are reused by the next batch).  What
+        the online filtered-BC loop feeds `offline_device.filter_records` / `mask_data_from_records`; no text, no host token data."""
+        import torch
+        from .algorithms.ppo_device import PPORecords
+        n_batches = -(-n_rollouts // self.B)
+        seeds_all = np.zeros((n_batches, self.B), dtype=np.uint64)
+        for k in range(n_batches):
+            n_k = min(n_rollouts - k * self.B, self.B)
+            seeds_all[k, :n_k] = [next(seed_generator) for _ in range(n_k)] if seed_generator is not None else np.random.randint(0, 2 ** 31 - 1, size=n_k)
+        key = (float(temperature), int(sample_seed), 0.0, False, int(top_k), float(top_p or 0.0))
+        want_graph = (getattr(self, "_eval_graph_key", None) == key or n_batches >= 4) if use_graph is None else bool(use_graph)
+        if want_graph:
+            seeds_dev = torch.from_numpy(seeds_all.view(np.int64)).to(self.dev)
+            if getattr(self, "_eval_graph_key", None) != key:
+                self.capture_episode(temperature=temperature, sample_seed=sample_seed, steer_strength=0.0, scripted=False, top_k=top_k, top_p=top_p or 0.0)
+                self._eval_graph_key = key
+        parts, stats = [], []
+        for k in range(n_batches):
+            n_k = min(n_rollouts - k * self.B, self.B)
+            if want_graph:
+                self.replay_episode(seeds_dev[k], None)
+            else:
+                self.run_episode(seeds_all[k], temperature=temperature, top_k=top_k, top_p=top_p or 0.0, sample_seed=sample_seed + (self.episodes << 20))
+                self.episodes += 1
+            r = self.ppo_records(n_k)
+            parts.append([x.clone() for x in (r.tokens, r.is_action, r.reward, r.n_tok, r.done)])
+            stats.append(np.stack([self.traj[name][:n_k].cpu().numpy().astype(np.float64) for name in ("ep_reward", "env_done", "n_steps")]))
+        rec = PPORecords(*[torch.cat([p[i] for p in parts]).contiguous() for i in range(5)])
+        st = np.concatenate(stats, axis=1)
+        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
+        return rec, dict(reward=summ(st[0].astype(np.float32)), done=summ(st[1].astype(np.float32)), length=summ(st[2].astype(np.int64)))
+
     # ---- the script-level call on the device engine -----------------------------------------------------------------
     def interactions(self, decode=None):
         """The finished episode as `List[List[InteractionTransition]]` — what `interact_environment` returns for the same

@@ -4,6 +4,8 @@
     python scripts/harness.py ppo      [--bc-data d.jsonl]                           # llm_rl_scripts/wordle/ppo/train_ppo_gpt2.py
     python scripts/harness.py ppo      --env maze --device-rollouts 1                # llm_rl_scripts/maze/ppo/train_ppo_online.py (device-resident loop)
     python scripts/harness.py ppo      --env chess --device-rollouts 1               # llm_rl_scripts/chess/ppo/train_ppo_gpt2_online.py (device-resident loop)
+    python scripts/harness.py ilql     --device-data 1 --policy mixture --n-data 1000  # the data played and blocked on the device, device batches
+    python scripts/harness.py filtered-bc --device-rollouts 1 --device-data 1        # wordle/online_filtered_bc, every round resident in HBM
     python scripts/harness.py bc-eval                                                # llm_rl_scripts/wordle/bc/eval_bc_gpt2.py
     python scripts/harness.py maze-eval                                              # llm_rl_scripts/maze/bc/fully_observed_bc.py (eval part)
     python scripts/harness.py gen-data --n-data 1000 --out d.jsonl                   # llm_rl_scripts/wordle/misc/data_gen.py
@@ -173,8 +175,21 @@ def cmd_ilql(a):
                             target_base=target_base, lr=a.lr, weight_decay=a.weight_decay, grad_accum_steps=a.grad_accum_steps,
                             polyak_alpha=a.polyak_alpha, hard_update_every=None if a.hard_update_every is None else int(a.hard_update_every))
     bs = BlockingStrategy(Padding.RIGHT, Truncation.RIGHT, a.max_length)
-    train = DS.ilql_dataset_from_jsonl(a.train_data, tok, bs)
     vocab, env = _wordle_env(a)
+    if a.device_data:
+        # --device-data 1: the gen-data policy plays on the device and its records become the blocked dataset where they lie
+        # (datasets.wordle_offline_dataset_device): no jsonl file, no host tokenizer; the train steps take the device batches
+        from lmrl_gym_amd.rollout import WordleTokenTable
+        table = getattr(tok, "table", None) or WordleTokenTable.from_tokenizer(tok)
+        train = DS.wordle_offline_dataset_device(vocab, a.n_data, _scripted_policy(a, vocab), tokens=table, kind="ilql", seed=a.data_seed, bsize=a.data_bsize,
+                                                 max_length=a.max_length, bad_word_reward=a.bad_word_reward)
+        _log("device_data", dict(episodes=len(train), longest=train.longest, width=int(train.input_ids.shape[1]), policy=a.policy))
+        batches = lambda epoch: train.batches(np.random.default_rng(epoch), a.train_bsize, truncate=True)
+    else:
+        if not a.train_data:
+            raise SystemExit("ilql: give --train-data FILE, or --device-data 1 to play the data on the device")
+        train = DS.ilql_dataset_from_jsonl(a.train_data, tok, bs)
+        batches = lambda epoch: DS.dataloader(np.random.default_rng(epoch), train, a.train_bsize, truncate=True)
 
     def evaluate():
         # --policy-engine f32 / bf16x3: the heads as the trainer holds them, unrounded (GPT2EngineF32.value_head)
@@ -198,9 +213,12 @@ def cmd_ilql(a):
 
     step = 0
     for epoch in range(a.epochs):
-        for batch in DS.dataloader(np.random.default_rng(epoch), train, a.train_bsize, truncate=True):
-            _, loss, logs = tr.step(batch["input_ids"], batch["should_take_action"], batch["rewards"], batch["dones"],
-                                    next_token_ids=batch["next_token_ids"], next_dones=batch["next_dones"])
+        for batch in batches(epoch):
+            if a.device_data:
+                _, loss, logs = tr.step(**batch)
+            else:
+                _, loss, logs = tr.step(batch["input_ids"], batch["should_take_action"], batch["rewards"], batch["dones"],
+                                        next_token_ids=batch["next_token_ids"], next_dones=batch["next_dones"])
             step += 1
             if step % a.log_every == 0 or step == 1:
                 _log("train", dict(step=step, epoch=epoch, loss=loss, losses=logs["losses"]))
@@ -386,6 +404,41 @@ def cmd_filtered_bc(a):
     bs = BlockingStrategy(Padding.RIGHT, Truncation.LEFT, a.max_input_length + a.max_output_length)
     step = 0
     limit = None if a.max_steps is None else int(a.max_steps)
+    if a.device_data:
+        # --device-data 1: the round never leaves the device — records -> filter_records (one [n] score readback) -> DeviceMaskDataset -> steps on
+        # device batches -> the trainer's parameters into the SAME engine in place (captured episodes stay valid)
+        if not a.device_rollouts:
+            raise SystemExit("filtered-bc --device-data 1 needs --device-rollouts 1")
+        from lmrl_gym_amd.algorithms import offline_device as OD
+        ro = _device_rollouts(policy.engine, vocab, tok, a.rollout_bsize, a.bad_word_reward, min(a.max_output_length, 12))
+        for rnd in range(a.n_rounds):
+            if limit is not None and step >= limit:
+                break
+            rec, summary = ro.record_rollouts(a.n_rollouts, seed_generator=iter(range(rnd * 10 ** 6, 10 ** 9)), temperature=a.policy_temperature or 1.0,
+                                              top_k=int(a.policy_top_k or 0), top_p=float(a.policy_top_p or 0.0), sample_seed=rnd)
+            keep = OD.filter_records(rec, top_fraction=a.filter_percengage)
+            kept = [int(i) for i in keep.rows_host]
+            scores = OD.record_returns(rec).cpu().numpy()
+            _log("data_collection", dict(round=rnd, env_interaction=summary, kept=len(kept), kept_episodes=kept,
+                                         reward_cutoff=min((float(scores[i]) for i in kept), default=None), device_resident=True))
+            if not kept:
+                continue
+            ds = OD.mask_data_from_records(rec, bs, tok.pad_token_id, keep=keep)
+            for epoch in range(a.epochs):
+                if limit is not None and step >= limit:
+                    break
+                for batch in ds.batches(np.random.default_rng(rnd * 1000 + epoch), min(a.train_bsize, len(ds)), truncate=True):
+                    _, loss, _ = tr.step(**batch)
+                    step += 1
+                    _log("train", dict(step=step, round=rnd, loss=loss))
+                    if limit is not None and step >= limit:
+                        break
+            ro.load_params(model.p)
+        _, summary = ro.record_rollouts(a.n_rollouts, seed_generator=iter(range(10 ** 8, 10 ** 9)), temperature=a.policy_temperature or 1.0,
+                                        top_k=int(a.policy_top_k or 0), top_p=float(a.policy_top_p or 0.0), sample_seed=a.n_rounds)
+        ro.close()
+        _log("eval", summary)
+        return
     for rnd in range(a.n_rounds):
         if limit is not None and step >= limit:      # the step budget ends the run: no further rollouts, epochs or rounds
             break
@@ -400,7 +453,8 @@ def cmd_filtered_bc(a):
         segs = [[(t.text, float(t.is_action)) for t in ep[-1].post_transition_history] for ep in raw]
         rewards = [sum(t.reward for t in ep) for ep in raw]
         top = sorted(range(len(segs)), key=lambda i: rewards[i], reverse=True)[: int(len(segs) * a.filter_percengage)]
-        _log("data_collection", dict(round=rnd, env_interaction=summary, kept=len(top), reward_cutoff=min((rewards[i] for i in top), default=None)))
+        _log("data_collection", dict(round=rnd, env_interaction=summary, kept=len(top), kept_episodes=list(top),
+                                     reward_cutoff=min((rewards[i] for i in top), default=None)))
         if not top:
             continue
         ds = DS.MaskDataset.blocked_from_str_segments([segs[i] for i in top], tok, bs)
@@ -471,7 +525,16 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--rollout-lanes", type=int, default=1, help="device rollouts: independent episode batches in flight at once "
                                                                      "(WordleRolloutEngine.text_env_eval(concurrent=n); >= 4 batches use the graph path)")
         _add(p, defaults)
-    sub.choices["ilql"].add_argument("--train-data", required=True)
+    sub.choices["ilql"].add_argument("--train-data", default=None)
+    for name in ("ilql", "filtered-bc"):
+        sub.choices[name].add_argument("--device-data", type=int, default=0,
+                                       help="1 = datasets are built on the device from rollout records and the train steps take device batches: ilql plays "
+                                            "--n-data episodes of the gen-data --policy instead of reading --train-data; filtered-bc (with --device-rollouts 1) "
+                                            "keeps every round in HBM and loads the new weights into the engine in place")
+    il = sub.choices["ilql"]
+    il.add_argument("--n-data", type=int, default=1000); il.add_argument("--prob-smart", type=float, default=0.5)
+    il.add_argument("--policy", default="mixture", choices=["mixture", "optimal", "optimal-mixture"]); il.add_argument("--mix-prob", type=float, default=0.5)
+    il.add_argument("--start-word", default="none"); il.add_argument("--data-seed", type=int, default=0); il.add_argument("--data-bsize", type=int, default=1024)
     sub.choices["ilql"].add_argument("--eval-data", default=None)
     sub.choices["ilql"].add_argument("--policy-engine", default="bf16", choices=["bf16", "f32", "bf16x3"],
                                      help="evaluation engines of pi_beta and the value base: bf16 GPT2Engine (default) or GPT2EngineF32 in that matmul mode "

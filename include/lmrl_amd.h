@@ -1102,6 +1102,26 @@ int lmrl_flash_attn_bwd_staged(const float *qkv_d, const uint8_t *key_mask_d, co
  * called with att_d = NULL: no fp32 copy of the attention output exists in the bf16-matmul train mode. */
 int lmrl_flash_attn_bwd_staged_attb(const float *qkv_d, const uint8_t *key_mask_d, const void *att_bf16_d, long ld_att, const float *datt_d, const float *lse_d,
                                     void *dqkv_bf16_d, long ldb, void *ws_d, int batch, int heads, int t, int qkv_staged, void *stream);
+/* ---- dropout of the train step (csrc/dropout.h, dropout.hip; DESIGN.md "Dropout").  Keep masks come from a counter-based stream and are never
+ * stored: a forward call has a key (k0, k1); site s (0: embedding output, 1 + 3 l: attention probabilities of block l, 2 + 3 l / 3 + 3 l: output
+ * of the attention / MLP c_proj of block l) draws with K_s = threefry2x32(K, (0, s)); element i (row-major in the site's tensor of n < 2^32
+ * elements) is kept iff the uniform of word i of jax.random.bits(K_s, (n,)) is < 1 - p, and kept values are multiplied by 1 / (1 - p).
+ * lmrl_dropout_host_mask: the keep bytes (1 / 0) of a whole site on the host, for tests without a GPU (p = 0 allowed: all ones). */
+int lmrl_dropout_host_mask(uint32_t k0, uint32_t k1, uint32_t site, uint64_t n, float p, uint8_t *out);
+/* y = x * mask / (1 - p), 0 < p < 1; y_d may be x_d.  The forward applies it in place; the backward calls it on dy with the same arguments. */
+int lmrl_dropout_apply(const float *x_d, float *y_d, uint64_t n, uint32_t k0, uint32_t k1, uint32_t site, float p, void *stream);
+/* the same from fp32 x [rows][cols] into the bf16 operand dst [rows_dst][ldb] of a backward product (zero beyond rows / cols), n = rows * cols */
+int lmrl_dropout_apply_bf16(const float *x_d, int rows, int cols, void *dst_d, long ldb, int rows_dst, uint32_t k0, uint32_t k1, uint32_t site, float p,
+                            void *stream);
+/* the flash attention sweeps with dropout on the probabilities (site tensor [batch][heads][t][t]); both arithmetic modes run the generic sweeps.
+ * Arguments as lmrl_flash_attn_fwd / _fwd_staged (att_bf16_d NULL: no bf16 copy; att_d NULL in bf16 mode: no fp32 output) and as
+ * lmrl_flash_attn_bwd / _bwd_staged / _bwd_staged_attb (exactly one of dqkv_d, dqkv_bf16_d; att_d NULL: D from att_bf16_d).  lse_d is the
+ * log-sum-exp of the UNDROPPED scores. */
+int lmrl_flash_attn_fwd_dropout(const float *qkv_d, const uint8_t *key_mask_d, float *att_d, float *lse_d, void *ws_d, void *att_bf16_d, long ldb, int batch,
+                                int heads, int t, int bf16, uint32_t k0, uint32_t k1, uint32_t site, float p, void *stream);
+int lmrl_flash_attn_bwd_dropout(const float *qkv_d, const uint8_t *key_mask_d, const float *att_d, const void *att_bf16_d, long ld_att, const float *datt_d,
+                                const float *lse_d, float *dqkv_d, void *dqkv_bf16_d, long ldb, void *ws_d, int batch, int heads, int t, int bf16,
+                                int qkv_staged, uint32_t k0, uint32_t k1, uint32_t site, float p, void *stream);
 /* ---- bf16-MFMA matmul mode of the train step (csrc/train_bf16.hip): the reference's optional `bf16_activations`
  * (train_ilql_gpt2.py:193; model dtype bf16, fp32 parameters).  Operands are staged as K-major bf16 matrices for lmrl_gemm_bf16.
  * lmrl_cast_bf16: dst [rows_dst][ld_dst] bf16 := round-to-nearest-even of src [rows][cols] fp32 (transpose = 0) or of its transpose

@@ -199,6 +199,14 @@ _SIGS = {
     "lmrl_flash_attn_finish_staging": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "lmrl_flash_attn_bwd_staged": (c_int, [c_void_p] * 6 + [ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "lmrl_flash_attn_bwd_staged_attb": (c_int, [c_void_p] * 3 + [ctypes.c_long] + [c_void_p] * 3 + [ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "lmrl_dropout_host_mask": (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, c_float, c_void_p]),
+    "lmrl_dropout_apply": (c_int, [c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_float, c_void_p]),
+    "lmrl_dropout_apply_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, ctypes.c_long, c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_float,
+                                        c_void_p]),
+    "lmrl_flash_attn_fwd_dropout": (c_int, [c_void_p] * 6 + [ctypes.c_long, c_int, c_int, c_int, c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_float,
+                                            c_void_p]),
+    "lmrl_flash_attn_bwd_dropout": (c_int, [c_void_p] * 4 + [ctypes.c_long] + [c_void_p] * 4 + [ctypes.c_long, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_float, c_void_p]),
     "lmrl_adamw_segments": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p]),
     "lmrl_adamw_segments_polyak": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_int,
                                            c_void_p, c_float, c_float, c_void_p]),

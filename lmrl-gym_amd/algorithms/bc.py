@@ -39,16 +39,17 @@ def bc_weights(attention_mask: np.ndarray, is_action: np.ndarray, non_action_wei
 
 
 def masked_ce_forward_backward(m: GPT2F32, ids: np.ndarray, am: np.ndarray, pos: np.ndarray, w: np.ndarray, denom: float,
-                               grads=None, grad_scale: float = 1.0, compact_rows: bool = True) -> float:
+                               grads=None, grad_scale: float = 1.0, compact_rows: bool = True, dropout_key=None) -> float:
     """loss = sum(w * CE(logits[:, :-1], ids[:, 1:])) / denom with the masked sums all-reduced across ranks; when `grads`
-    is given, grad_scale * d loss / d params is ACCUMULATED into it (shared by the BC trainer and the PPO BC term)."""
+    is given, grad_scale * d loss / d params is ACCUMULATED into it (shared by the BC trainer and the PPO BC term).
+    dropout_key: the forward key of the model call (`dropout_rng` of bc_loss, bc/interface.py:39)."""
     import torch
     from .ppo import _on_device
     on_dev = _on_device(ids)
     B, T = ids.shape
     R, dev = B * T, m.dev
     ids_d = _t(ids, np.int32)
-    hid, cache = m.forward(ids_d, _t(am, np.uint8), _t(pos, np.int32))
+    hid, cache = m.forward(ids_d, _t(am, np.uint8), _t(pos, np.int32), dropout_key=dropout_key)
     if D.is_distributed():
         denom = float(D.allreduce_sum_(torch.tensor([denom], dtype=torch.float64, device=dev)).item())
     if on_dev:
@@ -121,9 +122,13 @@ class GPT2BCTrain:
         self.opt = AdamW(model.p, lr, weight_decay=weight_decay, every_k=grad_accum_steps)
         self.last_grads = None
 
-    def step(self, input_ids, is_action, attention_mask=None, position_ids=None, train: bool = True):
+    def step(self, input_ids, is_action, attention_mask=None, position_ids=None, train: bool = True, prng_key=None):
+        """prng_key (a `jax_prng.Key` or an int seed): the `rng` of the reference's step_fn, handed to the model as its dropout key WITHOUT a
+        split (bc/interface.py:121-131; the train loop splits once per step before it calls step_fn)."""
         import torch
+        from .common import dropout_step_keys
         from .ppo import _on_device
+        dropout_key = dropout_step_keys([self.model], prng_key, train).key
         if _on_device(input_ids):
             # a batch that never left the device (`offline_device.DeviceMaskDataset.batch`); one integer comes back: the normaliser sum(attn[:, 1:])
             from .mc_returns import _device_masks
@@ -136,7 +141,7 @@ class GPT2BCTrain:
             am, pos = initialize_attn_mask_pos_ids(ids, self.pad, attention_mask, position_ids)
             w, denom = bc_weights(am, is_action, self.w)
         grads = self.model.zero_grads() if train else None
-        loss = masked_ce_forward_backward(self.model, ids, am, pos, w, denom, grads)
+        loss = masked_ce_forward_backward(self.model, ids, am, pos, w, denom, grads, dropout_key=dropout_key)
         if not train:
             return self, loss, {"loss": np.float32(loss)}
         self.last_grads = grads

@@ -71,3 +71,14 @@ def stats_from_sums(sum_w, sum_b, sumsq_b, mn, mx, count_b, n) -> Dict[str, np.f
     mb = sum_b / count_b
     var = max(sumsq_b / count_b - mb * mb, 0.0)
     return dict(mean=f(sum_w / n), min=f(mn), max=f(mx), std=f(math.sqrt(var)))
+
+
+def dropout_step_keys(models, prng_key, train: bool):
+    """The `jax_prng.StepKeys` of one train step.  Dropout runs only under train=True (`eval_loss` and train=False never drop); train=True on a
+    model with a dropout rate > 0 and no key raises — flax would fail for want of a 'dropout' rng.  prng_key: a `jax_prng.Key` or an int seed."""
+    from ..jax_prng import StepKeys
+    if not train:
+        return StepKeys(None)
+    if prng_key is None and any(m is not None and m.has_dropout() for m in models):
+        raise ValueError("train=True on a model with dropout rates > 0 needs prng_key (a jax_prng.Key or an int seed)")
+    return StepKeys(prng_key)

@@ -16,7 +16,7 @@ from .. import _lib
 from .. import dist as D
 from ..train import ops
 from ..train.gpt2_f32 import AdamW, GPT2F32, MLPHeadF32
-from .common import BlockingStrategy, Padding, Truncation, block_sequences, initialize_attn_mask_pos_ids, stats_from_sums, masked_rows
+from .common import BlockingStrategy, Padding, Truncation, block_sequences, initialize_attn_mask_pos_ids, stats_from_sums, masked_rows, dropout_step_keys
 from .ppo import _on_device, _t
 
 
@@ -209,6 +209,12 @@ class GPT2ILQLTrain:
     def step(self, input_ids, should_take_action, rewards, dones, next_token_ids=None, next_dones=None, prng_key=None,
              attention_mask=None, position_ids=None, next_tokens_attention_mask=None, next_tokens_position_ids=None, train: bool = True):
         import torch
+        # dropout keys in the reference's order (interface.py:132-264): a split before the base forward, the target base forward (if there is
+        # one) and the next-token forward (if there is one), then one before each of the five head calls and the next-token V head (no dropout there)
+        keys = dropout_step_keys([self.base, self.target_base], prng_key, train)
+        k_base = keys.next()
+        k_target = keys.next() if self.target_base is not None else None
+        k_next = keys.next() if next_token_ids is not None else None
         on_dev = _on_device(input_ids)
         if on_dev:
             # a batch that never left the device (`offline_device.DeviceILQLDataset.batch`): masks, positions, the Q-head row list and its
@@ -229,8 +235,8 @@ class GPT2ILQLTrain:
         V = self.q1.dout
         if not on_dev:
             ids_d, pos_d, am_d = _t(ids, np.int32), _t(pos, np.int32), _t(am, np.uint8)
-        hid, cache = base.forward(ids_d, am_d, pos_d)
-        thid = self.target_base.forward(ids_d, am_d, pos_d, inference=True)[0] if self.target_base is not None else hid      # never differentiated
+        hid, cache = base.forward(ids_d, am_d, pos_d, dropout_key=k_base)
+        thid = self.target_base.forward(ids_d, am_d, pos_d, inference=True, dropout_key=k_target)[0] if self.target_base is not None else hid      # never differentiated
         vo, vc = self.v.forward(hid, R)
         tgt = torch.zeros(R, dtype=torch.int32, device=dev)
         tgt.view(B, T)[:, :-1] = ids_d[:, 1:]
@@ -296,7 +302,7 @@ class GPT2ILQLTrain:
             if next_token_ids is not None:
                 nids_d = _t(next_token_ids, np.int32)
                 nam_d, npos_d = _device_masks(nids_d, self.pad, next_tokens_attention_mask, next_tokens_position_ids)
-                nhid, ncache = base.forward(nids_d, nam_d, npos_d)
+                nhid, ncache = base.forward(nids_d, nam_d, npos_d, dropout_key=k_next)
                 rows = torch.arange(B, device=dev, dtype=torch.int64) * nids_d.shape[1] + last_one(nam_d)
                 final_h = nhid.index_select(0, rows).contiguous()
                 nv, _ = self.v.forward(final_h, B)
@@ -312,7 +318,7 @@ class GPT2ILQLTrain:
             d = np.asarray(dones, dtype=np.float32)
             nids = np.asarray(next_token_ids, dtype=np.int32)
             nam, npos = initialize_attn_mask_pos_ids(nids, self.pad, next_tokens_attention_mask, next_tokens_position_ids)
-            nhid, ncache = base.forward(_t(nids, np.int32), _t(nam, np.uint8), _t(npos, np.int32))
+            nhid, ncache = base.forward(_t(nids, np.int32), _t(nam, np.uint8), _t(npos, np.int32), dropout_key=k_next)
             last_idx = (nam.shape[1] - 1) - np.argmax(np.flip(nam, axis=1).astype(np.int32), axis=1)
             rows = torch.from_numpy((np.arange(B) * nids.shape[1] + last_idx).astype(np.int64)).to(dev)
             final_h = nhid.index_select(0, rows).contiguous()

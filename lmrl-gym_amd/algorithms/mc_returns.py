@@ -158,7 +158,9 @@ class GPT2MCTrain:
         R, base, dev, V = B * T, self.base, self.base.dev, self.q_head.dout
         if not on_dev:
             ids_d = _t(ids, np.int32)
-        hid, cache = base.forward(ids_d, _t(am, np.uint8), _t(pos, np.int32))
+        from .common import dropout_step_keys
+        keys = dropout_step_keys([base], prng_key, train)      # mc_returns/gpt2/interface.py:77-104: a split before the base forward (and one before the head)
+        hid, cache = base.forward(ids_d, _t(am, np.uint8), _t(pos, np.int32), dropout_key=keys.next())
         # the Q head runs on the rows the loss reads: should_take_action (the L2 term selects by it alone — q_query_indicators / a_mask,
         # mc_returns/base_interface.py:32-41; the CQL term and n also multiply by the attention mask, which the loss kernel applies) — see
         # GPT2ILQLTrain.compact_q_rows

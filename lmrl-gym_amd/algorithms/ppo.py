@@ -178,14 +178,14 @@ def ppo_loss_fn(attention_mask, logprobs, values, should_take_action, old_logpro
 
 
 # ----------------------------------------------------------------------------- data (ppo/data.py:9-114)
-def _masked_lm_term(policy, pad, input_ids, attention_mask, position_ids, training_mask, grads, grad_scale):
+def _masked_lm_term(policy, pad, input_ids, attention_mask, position_ids, training_mask, grads, grad_scale, dropout_key=None):
     """The BC auxiliary of PPO: JaxSeq `loss_fn_mask` as wired in llm_rl_scripts/wordle/ppo/train_ppo_gpt2.py —
     sum(CE * training_mask[:, 1:]) / sum(training_mask[:, 1:]) on a second batch (third-party arithmetic: parity unpinned)."""
     from .bc import masked_ce_forward_backward
     ids = np.asarray(input_ids, dtype=np.int32)
     am, pos = initialize_attn_mask_pos_ids(ids, pad, attention_mask, position_ids)
     tm = np.asarray(training_mask if training_mask is not None else am, dtype=np.float32)[:, 1:]
-    return masked_ce_forward_backward(policy, ids, am, pos, tm, float(tm.sum()), grads, grad_scale)
+    return masked_ce_forward_backward(policy, ids, am, pos, tm, float(tm.sum()), grads, grad_scale, dropout_key=dropout_key)
 
 
 class PPOData(NamedTuple):
@@ -257,16 +257,22 @@ class GPT2PPOTrain:
 
     compact_rows = True
 
-    def _bc_term(self, ids, am, pos, tmask, grads):
-        return _masked_lm_term(self.policy, self.pad, ids, am, pos, tmask, grads, self.bc_loss_weight)
+    def _bc_term(self, ids, am, pos, tmask, grads, dropout_key=None):
+        return _masked_lm_term(self.policy, self.pad, ids, am, pos, tmask, grads, self.bc_loss_weight, dropout_key=dropout_key)
 
     def step(self, input_ids, should_take_action, old_logprobs, old_values, old_advantages, old_returns, prng_key=None,
              attention_mask=None, position_ids=None, bc_data_input_ids=None, bc_data_input_attention_mask=None,
              bc_data_input_position_ids=None, bc_data_input_training_mask=None, train: bool = True):
         import torch
+        from ..jax_prng import StepKeys
+        from .common import dropout_step_keys
         pol, head = self.policy, self.value_head
         dev = pol.dev
         f32 = lambda x: _t(x, np.float32)
+        # dropout keys in the reference's order (ppo/gpt2/interface.py:106-190): the step splits once for grad_loss, which splits again before
+        # the policy forward (and before the value head); with a BC batch the step splits once more and hands that key to the BC loss
+        keys = dropout_step_keys([pol], prng_key, train)
+        k_policy = StepKeys(keys.next()).next()
         if _on_device(input_ids):
             # a batch that never left the device (`ppo_device.DevicePPODataset.batch`): masks, positions, the masked row list and its
             # next-token targets come from csrc/ppo_data.hip; the host learns one integer (the row count that sizes the LM-head product)
@@ -295,7 +301,7 @@ class GPT2PPOTrain:
             Ra = int(rows_h.size)
             idx, tgt_rows = _t(rows_h, np.int32), _t(ids[:, 1:][p_mask].astype(np.int32), np.int32)
             attn_s, sta_d = f32(am[:, 1:]), _t(should_take_action, np.uint8)
-        hid, cache = pol.forward(ids_d, am_d, pos_d)
+        hid, cache = pol.forward(ids_d, am_d, pos_d, dropout_key=k_policy)
         values_full, hcache = head.forward(hid, R)                               # [R, 1]
         compact = self.compact_rows and 0 < Ra < R
         if compact:
@@ -345,7 +351,8 @@ class GPT2PPOTrain:
         pol.backward(cache, d_hidden, pgrads, on_final=None if use_bc else red.ready(pgrads))
         if use_bc:   # policy_grads += bc_loss_weight * bc_grads ; loss += bc_loss_weight * bc_loss  (gpt2/interface.py:180-203)
             del cache, logits, d_hidden
-            bc_loss = self._bc_term(bc_data_input_ids, bc_data_input_attention_mask, bc_data_input_position_ids, bc_data_input_training_mask, pgrads)
+            bc_loss = self._bc_term(bc_data_input_ids, bc_data_input_attention_mask, bc_data_input_position_ids, bc_data_input_training_mask, pgrads,
+                                    dropout_key=keys.next())
             total = loss + bc_loss * self.bc_loss_weight
             loss, logs = total, {"ppo": logs, "bc": {"loss": np.float32(bc_loss)}, "total_loss": np.float32(total)}
         self.last_grads = (pgrads, hgrads)

@@ -209,6 +209,12 @@ def _load_params_dir(path: str) -> Tuple[Dict[str, Any], Dict[str, Any]]:
     raise FileNotFoundError(f"neither params.msgpack nor train_state.msgpack under {path}")
 
 
+def _pdrop_fields(cfg_json: Dict[str, Any]) -> Dict[str, float]:
+    """embd_pdrop / attn_pdrop / resid_pdrop of a GPT-2 `config.json`.  HF writes only the fields that differ from `GPT2Config()`'s defaults, so
+    a missing field means that default, 0.1.  The values land in the config object only — nothing applies them implicitly."""
+    return {k: float(cfg_json.get(k, 0.1)) for k in ("embd_pdrop", "attn_pdrop", "resid_pdrop")}
+
+
 def load_gpt2_checkpoint(path: str):
     """-> (GPT2Config, state_dict of float32 numpy arrays) from `<path>/{config.json, params.msgpack|train_state.msgpack}`."""
     from .gpt2 import GPT2Config
@@ -221,14 +227,15 @@ def load_gpt2_checkpoint(path: str):
     cfg = GPT2Config(n_layer=1 + max(int(k.split(".")[1]) for k in sd if k.startswith("h.")),
                      n_head=int(cfg_json["n_head"]), d_model=d, d_ff=sd["h.0.mlp.c_fc.weight"].shape[1],
                      vocab=sd["wte.weight"].shape[0], n_pos=sd["wpe.weight"].shape[0],
-                     ln_eps=float(cfg_json.get("layer_norm_epsilon", 1e-5)))
+                     ln_eps=float(cfg_json.get("layer_norm_epsilon", 1e-5)), **_pdrop_fields(cfg_json))
     return cfg, sd
 
 
 def save_gpt2_checkpoint(path: str, cfg, state_dict: Dict[str, Any], extra_config: Optional[Dict[str, Any]] = None) -> None:
     os.makedirs(path, exist_ok=True)
     cj = dict(model_type="gpt2", n_layer=cfg.n_layer, n_head=cfg.n_head, n_embd=cfg.d_model, n_inner=cfg.d_ff, vocab_size=cfg.vocab,
-              n_positions=cfg.n_pos, layer_norm_epsilon=cfg.ln_eps, activation_function="gelu_new")
+              n_positions=cfg.n_pos, layer_norm_epsilon=cfg.ln_eps, activation_function="gelu_new",
+              embd_pdrop=getattr(cfg, "embd_pdrop", 0.0), attn_pdrop=getattr(cfg, "attn_pdrop", 0.0), resid_pdrop=getattr(cfg, "resid_pdrop", 0.0))
     cj.update(extra_config or {})
     with open(os.path.join(path, "config.json"), "w") as f:
         json.dump(cj, f, indent=2)
@@ -267,5 +274,5 @@ def load_hf_pytorch_gpt2(path: str):
         sd[k] = np.asarray(v, dtype=np.float32)
     d = sd["wte.weight"].shape[1]
     cfg = GPT2Config(n_layer=cj["n_layer"], n_head=cj["n_head"], d_model=d, d_ff=cj.get("n_inner") or 4 * d, vocab=sd["wte.weight"].shape[0],
-                     n_pos=sd["wpe.weight"].shape[0], ln_eps=cj.get("layer_norm_epsilon", 1e-5))
+                     n_pos=sd["wpe.weight"].shape[0], ln_eps=cj.get("layer_norm_epsilon", 1e-5), **_pdrop_fields(cj))
     return cfg, sd

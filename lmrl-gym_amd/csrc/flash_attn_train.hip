@@ -17,6 +17,7 @@
 // Masking matches softmax_causal_fwd_kernel (train_ops.hip): keys c <= r with key_mask[b][c] != 0; a row with no valid key gives 0.
 #include "../../include/lmrl_amd.h"
 #include "gemm_bf16.h"
+#include "dropout.h"
 
 namespace lmrl {
 
@@ -136,6 +137,16 @@ __device__ __forceinline__ void load_key_valid(uint8_t *sM, const uint8_t *kmb, 
 // and 8*lq + 4 + e (second): 8 consecutive rows per lane
 __device__ __forceinline__ int slab_row(int lr) { return (lr >> 2) * 8 + (lr & 3); }
 
+// attention dropout (csrc/dropout.h): keep bits of this lane's 8 consecutive keys k0 .. k0 + 7 of query q of head bh — element
+// ((bh * T + q) * T + k) of the [B, H, T, T] probabilities.  Out-of-range (q, k) give arbitrary bits: those probabilities are exactly zero.
+__device__ __forceinline__ unsigned drop_keep8(const DropoutSite &ds, int bh, int T, int q, int k0) {
+    const uint32_t base = ((uint32_t)bh * (uint32_t)T + (uint32_t)q) * (uint32_t)T + (uint32_t)k0;
+    unsigned bits = 0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) bits |= (dropout_keep(ds, base + e) ? 1u : 0u) << e;
+    return bits;
+}
+
 // ------------------------------------------------------------------------------------------ operand staging
 // src [B*T][ld] fp32, columns col0 + h*64 + c  ->  natural Xn [BH][Tp][64] and transposed XT [BH][64][Tp] (zero rows / columns for t >= T)
 // 8 consecutive elements per lane: one 16-byte store (bf16) or two (fp32)
@@ -237,10 +248,13 @@ __global__ __launch_bounds__(256) void flash_zero_pad_rows_kernel(uint16_t *__re
 }
 
 // ------------------------------------------------------------------------------------------ forward
-template <class E, bool PF>
+// DROP: attention dropout.  l and lse stay those of the undropped probabilities; only the P fed to O += V^T.P is masked (the 1 / (1 - p)
+// factor rides in the final normalisation).
+template <class E, bool PF, bool DROP = false>
 __global__ __launch_bounds__(256) void flash_fwd_kernel(const typename E::T *__restrict__ Qn, const typename E::T *__restrict__ Kn,
                                                         const typename E::T *__restrict__ VT, const uint8_t *__restrict__ km, float *__restrict__ att,
-                                                        float *__restrict__ lse, int H, int T, int Tp, int d, uint16_t *__restrict__ att_b, long ldb) {
+                                                        float *__restrict__ lse, int H, int T, int Tp, int d, uint16_t *__restrict__ att_b, long ldb,
+                                                        DropoutSite dro) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *sK = smem, *sV = smem + E::TILE;
     uint8_t *sM = reinterpret_cast<uint8_t *>(smem + 2 * E::TILE);
@@ -335,6 +349,11 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const typename E::T *__r
         for (int i = 0; i < 4; i++) o[i] *= alpha;
 #pragma unroll
         for (int p = 0; p < 2; p++) {
+            if (DROP) {
+                const unsigned keep = drop_keep8(dro, bh, T, qi, kb * 64 + p * 32 + lq * 8);
+#pragma unroll
+                for (int e = 0; e < 8; e++) s[p][e] = ((keep >> e) & 1u) ? s[p][e] : 0.f;
+            }
             const typename E::Frag pf = make_frag(E(), s[p]);
 #pragma unroll
             for (int db = 0; db < 4; db++) o[db] = mma(E(), o[db], ld_frag_lds(E(), sV, db * 16 + lr, p * 32 + lq * 8), pf);
@@ -342,11 +361,14 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const typename E::T *__r
     }
     l += __shfl_xor(l, 16);
     l += __shfl_xor(l, 32);
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    float inv = l > 0.f ? 1.f / l : 0.f;
+    if (DROP) inv *= dro.scale;
     if (qi < T) {
+        if (!DROP || att) {      // (dropout, bf16-matmul mode: the forward may be asked for the bf16 output only)
 #pragma unroll
-        for (int db = 0; db < 4; db++)
-            *reinterpret_cast<f32x4 *>(att + ((long)b * T + qi) * d + h * 64 + db * 16 + lq * 4) = o[db] * inv;
+            for (int db = 0; db < 4; db++)
+                *reinterpret_cast<f32x4 *>(att + ((long)b * T + qi) * d + h * 64 + db * 16 + lq * 4) = o[db] * inv;
+        }
         if (att_b) {     // bf16 copy: the operand of the output projection in the bf16-matmul train mode
 #pragma unroll
             for (int db = 0; db < 4; db++) {
@@ -587,13 +609,14 @@ __global__ __launch_bounds__(64 * NW, 4) void flash_fwd2_bf16_kernel(const uint1
 }
 
 // ------------------------------------------------------------------------------------------ backward: dQ
-template <class E, bool PF>
+// DROP: dP = (mask / (1 - p)) (V.dO^T) is the gradient w.r.t. the undropped probabilities; D = rowsum(dO o O) = sum_k P dP as without dropout
+template <class E, bool PF, bool DROP = false>
 __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(const typename E::T *__restrict__ Qn, const typename E::T *__restrict__ Kn,
                                                            const typename E::T *__restrict__ Vn, const typename E::T *__restrict__ KT,
                                                            const typename E::T *__restrict__ dOn, const float *__restrict__ Dsum,
                                                            const float *__restrict__ lse, const uint8_t *__restrict__ km, float *__restrict__ dqkv,
                                                            uint16_t *__restrict__ dqb, long ldb,
-                                                           int H, int T, int Tp, int d) {
+                                                           int H, int T, int Tp, int d, DropoutSite dro) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *sK = smem, *sV = smem + E::TILE, *sKT = smem + 2 * E::TILE;
     uint8_t *sM = reinterpret_cast<uint8_t *>(smem + 3 * E::TILE);
@@ -658,6 +681,14 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(const typename E::T *
                 pa = mma(E(), pa, ld_frag_lds(E(), sV, p * 32 + ra, sl * 32 + lq * 8), dof[sl]);
                 pb = mma(E(), pb, ld_frag_lds(E(), sV, p * 32 + ra + 4, sl * 32 + lq * 8), dof[sl]);
             }
+            if (DROP) {
+                const unsigned keep = drop_keep8(dro, bh, T, qi, kb * 64 + p * 32 + lq * 8);
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    pa[e] = ((keep >> e) & 1u) ? pa[e] * dro.scale : 0.f;
+                    pb[e] = ((keep >> (e + 4)) & 1u) ? pb[e] * dro.scale : 0.f;
+                }
+            }
             float ds[8];
             if (plain) {      // below the diagonal, all 64 keys valid, all 64 queries real: no masking (see flash_fwd_kernel)
 #pragma unroll
@@ -694,13 +725,14 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(const typename E::T *
 }
 
 // ------------------------------------------------------------------------------------------ backward: dK, dV
-template <class E, bool PF>
+// DROP: dV += dO^T.(mask P)^T with the 1 / (1 - p) factor applied once to the finished dV; dS as in flash_bwd_dq_kernel
+template <class E, bool PF, bool DROP = false>
 __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const typename E::T *__restrict__ Qn, const typename E::T *__restrict__ Kn,
                                                             const typename E::T *__restrict__ Vn, const typename E::T *__restrict__ QT,
                                                             const typename E::T *__restrict__ dOn, const typename E::T *__restrict__ dOT,
                                                             const float *__restrict__ Dsum, const float *__restrict__ lse,
                                                             const uint8_t *__restrict__ km, float *__restrict__ dqkv, uint16_t *__restrict__ dqb,
-                                                            long ldb, int H, int T, int Tp, int d) {
+                                                            long ldb, int H, int T, int Tp, int d, DropoutSite dro) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *sQ = smem, *sdO = smem + E::TILE, *sQT = smem + 2 * E::TILE, *sdOT = smem + 3 * E::TILE;
     float *sL = reinterpret_cast<float *>(smem + 4 * E::TILE), *sD = sL + 64;
@@ -762,6 +794,20 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const typename E::T 
                 pa = mma(E(), pa, ld_frag_lds(E(), sdO, p * 32 + ra, sl * 32 + lq * 8), vf[sl]);
                 pb = mma(E(), pb, ld_frag_lds(E(), sdO, p * 32 + ra + 4, sl * 32 + lq * 8), vf[sl]);
             }
+            unsigned keep = 0xffu;
+            if (DROP) {      // this lane: key kj x 8 consecutive queries — eight separate rows of the mask
+                keep = 0;
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const uint32_t qq = (uint32_t)(qb * 64 + p * 32 + lq * 8 + e);
+                    keep |= (dropout_keep(dro, ((uint32_t)bh * (uint32_t)T + qq) * (uint32_t)T + (uint32_t)kj) ? 1u : 0u) << e;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    pa[e] = ((keep >> e) & 1u) ? pa[e] * dro.scale : 0.f;
+                    pb[e] = ((keep >> (e + 4)) & 1u) ? pb[e] * dro.scale : 0.f;
+                }
+            }
             float pr[8], ds[8];
             if (all_keys_ok && qb > kb && qb * 64 + 63 < T) {      // workgroup-uniform: no masking on this block
 #pragma unroll
@@ -781,6 +827,10 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const typename E::T 
                     ds[e] = pr[e] * (dp - sD[ql]);
                 }
             }
+            if (DROP) {
+#pragma unroll
+                for (int e = 0; e < 8; e++) pr[e] = ((keep >> e) & 1u) ? pr[e] : 0.f;      // (ds above was formed from the undropped P)
+            }
             const typename E::Frag pf = make_frag(E(), pr), dsf = make_frag(E(), ds);
 #pragma unroll
             for (int db = 0; db < 4; db++) {
@@ -788,6 +838,10 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const typename E::T 
                 dk[db] = mma(E(), dk[db], ld_frag_lds(E(), sQT, db * 16 + lr, p * 32 + lq * 8), dsf);
             }
         }
+    }
+    if (DROP) {
+#pragma unroll
+        for (int db = 0; db < 4; db++) dv[db] *= dro.scale;
     }
     if (kj < T) {
 #pragma unroll
@@ -1073,13 +1127,27 @@ static int flash_stage_qkv(const float *qkv, const FlashWs &w, int batch, int he
 
 template <class E>
 static int flash_fwd(const float *qkv, const uint8_t *km, float *att, float *lse, void *ws, int batch, int heads, int t, hipStream_t s,
-                     void *att_b = nullptr, long ldb = 0) {
+                     void *att_b = nullptr, long ldb = 0, const DropoutSite *drop = nullptr) {
     typedef typename E::T T;
     const int tp = (t + 63) / 64 * 64, bh = batch * heads, d = heads * 64;
     FlashWs w; w.carve(ws, bh, tp, E::SZ);
     if (qkv) {             // null: the six q / k / v matrices are already staged in ws (lmrl_gemm_bf16_qkv_heads + lmrl_flash_attn_finish_staging)
         int rc = flash_stage_qkv<E>(qkv, w, batch, heads, t, tp, s);
         if (rc) return rc;
+    }
+    if (drop) {
+        // attention dropout runs on the generic sweeps in both arithmetic modes (the tuned bf16 kernels have no dropout variant: DESIGN.md);
+        // they read V^T, which the c_attn epilogue's staging (qkv null) leaves out unless a round-3 variant is selected
+        if (E::SZ == 2 && !qkv)
+            hipLaunchKernelGGL(flash_transpose_staged_kernel, dim3(tp / 64, bh, 3), dim3(256), 0, s, (uint16_t *)w.Qn, (uint16_t *)w.QT,
+                               (long)(FlashWs::mat_bytes(bh, tp, 2) / 2), t, tp);
+        const size_t lds = 2 * E::TILE + 64;
+        constexpr bool PF = FlashPrefetch<E>::fwd;
+        LMRL_CHECK_HIP(allow_lds(flash_fwd_kernel<E, PF, true>, lds));
+        hipLaunchKernelGGL((flash_fwd_kernel<E, PF, true>), dim3(tp / 64, bh), dim3(256), lds, s, (const T *)w.Qn, (const T *)w.Kn, (const T *)w.VT, km, att, lse,
+                           heads, t, tp, d, (uint16_t *)att_b, ldb, *drop);
+        LMRL_CHECK_LAUNCH();
+        return LMRL_OK;
     }
     if constexpr (E::SZ == 2) {
         if (!(g_flash_variant & 1)) {
@@ -1121,14 +1189,15 @@ static int flash_fwd(const float *qkv, const uint8_t *km, float *att, float *lse
     constexpr bool PF = FlashPrefetch<E>::fwd;
     LMRL_CHECK_HIP(allow_lds(flash_fwd_kernel<E, PF>, lds));
     hipLaunchKernelGGL((flash_fwd_kernel<E, PF>), dim3(tp / 64, bh), dim3(256), lds, s, (const T *)w.Qn, (const T *)w.Kn, (const T *)w.VT, km, att, lse, heads,
-                       t, tp, d, (uint16_t *)att_b, ldb);
+                       t, tp, d, (uint16_t *)att_b, ldb, DropoutSite{});
     LMRL_CHECK_LAUNCH();
     return LMRL_OK;
 }
 
 template <class E>
 static int flash_bwd(const float *qkv, const uint8_t *km, const float *att, const float *datt, const float *lse, float *dqkv, uint16_t *dqb,
-                     long ldb, void *ws, int batch, int heads, int t, hipStream_t s, int qkv_staged, const uint16_t *att_b = nullptr, long ld_attb = 0) {
+                     long ldb, void *ws, int batch, int heads, int t, hipStream_t s, int qkv_staged, const uint16_t *att_b = nullptr, long ld_attb = 0,
+                     const DropoutSite *drop = nullptr) {
     typedef typename E::T T;
     const int tp = (t + 63) / 64 * 64, bh = batch * heads, d = heads * 64;
     FlashWs w; w.carve(ws, bh, tp, E::SZ);
@@ -1136,14 +1205,14 @@ static int flash_bwd(const float *qkv, const uint8_t *km, const float *att, cons
         int rc = flash_stage_qkv<E>(qkv, w, batch, heads, t, tp, s);
         if (rc) return rc;
     }
-    if (E::SZ == 2 && qkv_staged && (g_flash_variant & 6)) {
+    if (E::SZ == 2 && qkv_staged && ((g_flash_variant & 6) || drop)) {
         // a round-3 bf16 sweep is selected NOW: it reads Q^T / K^T, which the forward's staging wrote only if a round-3 bit was set THEN
         // (lmrl_flash_attn_finish_staging).  Derive them here from the natural forms, so a variant flipped between a forward and its backward
         // (tools / A-B tests) cannot make the sweeps read uninitialised transposes; the default path (variant 0) never gets here.
         hipLaunchKernelGGL(flash_transpose_staged_kernel, dim3(tp / 64, bh, 3), dim3(256), 0, s, (uint16_t *)w.Qn, (uint16_t *)w.QT,
                            (long)(FlashWs::mat_bytes(bh, tp, 2) / 2), t, tp);
     }
-    const bool need_dot = E::SZ != 2 || (g_flash_variant & 6) != 0;         // fp32 sweeps and the round-3 bf16 dQ / dK/dV read dO^T
+    const bool need_dot = E::SZ != 2 || (g_flash_variant & 6) != 0 || drop;         // fp32 sweeps and the round-3 bf16 dQ / dK/dV (dropout: those) read dO^T
     hipLaunchKernelGGL(flash_stage_kernel<E>, dim3(tp / 64, bh), dim3(256), 0, s, datt, (long)d, 0, 1.f, (T *)w.dOn, need_dot ? (T *)w.dOT : (T *)nullptr, att, w.D,
                        heads, t, tp, att ? (const uint16_t *)nullptr : att_b, ld_attb);
     LMRL_CHECK_LAUNCH();
@@ -1152,6 +1221,16 @@ static int flash_bwd(const float *qkv, const uint8_t *km, const float *att, cons
     constexpr bool BF = E::SZ == 2;
     constexpr int NW = 8;
     const int nt = (tp + 16 * NW - 1) / (16 * NW);
+    if (drop) {
+        LMRL_CHECK_HIP(allow_lds(flash_bwd_dq_kernel<E, PFQ, true>, lds_q));
+        hipLaunchKernelGGL((flash_bwd_dq_kernel<E, PFQ, true>), dim3(tp / 64, bh), dim3(256), lds_q, s, (const T *)w.Qn, (const T *)w.Kn, (const T *)w.Vn,
+                           (const T *)w.KT, (const T *)w.dOn, (const float *)w.D, lse, km, dqkv, dqb, ldb, heads, t, tp, d, *drop);
+        LMRL_CHECK_HIP(allow_lds(flash_bwd_dkv_kernel<E, PFKV, true>, lds_kv));
+        hipLaunchKernelGGL((flash_bwd_dkv_kernel<E, PFKV, true>), dim3(tp / 64, bh), dim3(256), lds_kv, s, (const T *)w.Qn, (const T *)w.Kn, (const T *)w.Vn,
+                           (const T *)w.QT, (const T *)w.dOn, (const T *)w.dOT, (const float *)w.D, lse, km, dqkv, dqb, ldb, heads, t, tp, d, *drop);
+        LMRL_CHECK_LAUNCH();
+        return LMRL_OK;
+    }
     if (BF && !(g_flash_variant & 2)) {
         const size_t lds2 = 4 * E::TILE;
         LMRL_CHECK_HIP(allow_lds(flash_bwd2_dq_bf16_kernel<NW>, lds2));
@@ -1160,7 +1239,7 @@ static int flash_bwd(const float *qkv, const uint8_t *km, const float *att, cons
     } else {
         LMRL_CHECK_HIP(allow_lds(flash_bwd_dq_kernel<E, PFQ>, lds_q));
         hipLaunchKernelGGL((flash_bwd_dq_kernel<E, PFQ>), dim3(tp / 64, bh), dim3(256), lds_q, s, (const T *)w.Qn, (const T *)w.Kn, (const T *)w.Vn, (const T *)w.KT,
-                           (const T *)w.dOn, (const float *)w.D, lse, km, dqkv, dqb, ldb, heads, t, tp, d);
+                           (const T *)w.dOn, (const float *)w.D, lse, km, dqkv, dqb, ldb, heads, t, tp, d, DropoutSite{});
     }
     if (BF && !(g_flash_variant & 4)) {
         const size_t lds2 = 2 * (2 * E::TILE + 512);
@@ -1170,7 +1249,7 @@ static int flash_bwd(const float *qkv, const uint8_t *km, const float *att, cons
     } else {
         LMRL_CHECK_HIP(allow_lds(flash_bwd_dkv_kernel<E, PFKV>, lds_kv));
         hipLaunchKernelGGL((flash_bwd_dkv_kernel<E, PFKV>), dim3(tp / 64, bh), dim3(256), lds_kv, s, (const T *)w.Qn, (const T *)w.Kn, (const T *)w.Vn,
-                           (const T *)w.QT, (const T *)w.dOn, (const T *)w.dOT, (const float *)w.D, lse, km, dqkv, dqb, ldb, heads, t, tp, d);
+                           (const T *)w.QT, (const T *)w.dOn, (const T *)w.dOT, (const float *)w.D, lse, km, dqkv, dqb, ldb, heads, t, tp, d, DropoutSite{});
     }
     LMRL_CHECK_LAUNCH();
     return LMRL_OK;
@@ -1250,6 +1329,44 @@ int lmrl_flash_attn_bwd_staged_attb(const float *qkv_d, const uint8_t *key_mask_
                      ldb % 4 == 0 && batch > 0 && heads > 0 && t > 0, "lmrl_flash_attn_bwd_staged_attb: bad argument");
     return flash_bwd<ElemBF16>(qkv_d, key_mask_d, nullptr, datt_d, lse_d, nullptr, (uint16_t *)dqkv_bf16_d, ldb, ws_d, batch, heads, t, as_stream(stream),
                                qkv_staged, (const uint16_t *)att_bf16_d, ld_att);
+}
+
+// ---- attention dropout (csrc/dropout.h: key (k0, k1) of the forward call, site 1 + 3 * block, rate 0 < p < 1).  One entry each way for both
+// arithmetic modes: bf16 = 0 takes fp32 qkv_d / att_d / dqkv_d; bf16 = 1 the staged forms of lmrl_flash_attn_fwd_staged /
+// lmrl_flash_attn_bwd_staged(_attb) (null pointers as there).  lse_d is that of the UNDROPPED probabilities.
+static int flash_drop_site(DropoutSite &ds, int batch, int heads, int t, uint32_t k0, uint32_t k1, uint32_t site, float p) {
+    const uint64_t n = (uint64_t)batch * heads * (uint64_t)t * (uint64_t)t;
+    LMRL_REQUIRE(n < (1ull << 32), "flash attention dropout: a dropout site holds fewer than 2^32 elements");
+    LMRL_REQUIRE(p > 0.f && p < 1.f, "flash attention dropout: the rate must lie in (0, 1)");
+    ds = dropout_site(k0, k1, site, (uint32_t)n, p);
+    return LMRL_OK;
+}
+
+int lmrl_flash_attn_fwd_dropout(const float *qkv_d, const uint8_t *key_mask_d, float *att_d, float *lse_d, void *ws_d, void *att_bf16_d, long ldb, int batch,
+                                int heads, int t, int bf16, uint32_t k0, uint32_t k1, uint32_t site, float p, void *stream) {
+    LMRL_REQUIRE((qkv_d || bf16) && (att_d || (bf16 && att_bf16_d)) && lse_d && ws_d && (!att_bf16_d || (ldb >= heads * 64 && ldb % 4 == 0)) && batch > 0 &&
+                     heads > 0 && t > 0, "lmrl_flash_attn_fwd_dropout: bad argument");
+    DropoutSite ds;
+    int rc = flash_drop_site(ds, batch, heads, t, k0, k1, site, p);
+    if (rc) return rc;
+    return bf16 ? flash_fwd<ElemBF16>(qkv_d, key_mask_d, att_d, lse_d, ws_d, batch, heads, t, as_stream(stream), att_bf16_d, ldb, &ds)
+                : flash_fwd<ElemF32>(qkv_d, key_mask_d, att_d, lse_d, ws_d, batch, heads, t, as_stream(stream), att_bf16_d, ldb, &ds);
+}
+
+int lmrl_flash_attn_bwd_dropout(const float *qkv_d, const uint8_t *key_mask_d, const float *att_d, const void *att_bf16_d, long ld_att, const float *datt_d,
+                                const float *lse_d, float *dqkv_d, void *dqkv_bf16_d, long ldb, void *ws_d, int batch, int heads, int t, int bf16,
+                                int qkv_staged, uint32_t k0, uint32_t k1, uint32_t site, float p, void *stream) {
+    LMRL_REQUIRE((qkv_d || qkv_staged) && (att_d || (att_bf16_d && ld_att >= heads * 64 && ld_att % 4 == 0)) && datt_d && lse_d && ws_d && batch > 0 &&
+                     heads > 0 && t > 0, "lmrl_flash_attn_bwd_dropout: bad argument");
+    LMRL_REQUIRE((dqkv_d != nullptr) != (dqkv_bf16_d != nullptr) && (!dqkv_bf16_d || (bf16 && ldb >= 3 * heads * 64 && ldb % 4 == 0)),
+                 "lmrl_flash_attn_bwd_dropout: exactly one of dqkv_d / dqkv_bf16_d (bf16 mode, pitch >= 3 d)");
+    DropoutSite ds;
+    int rc = flash_drop_site(ds, batch, heads, t, k0, k1, site, p);
+    if (rc) return rc;
+    return bf16 ? flash_bwd<ElemBF16>(qkv_d, key_mask_d, att_d, datt_d, lse_d, dqkv_d, (uint16_t *)dqkv_bf16_d, ldb, ws_d, batch, heads, t, as_stream(stream),
+                                      qkv_staged, att_d ? nullptr : (const uint16_t *)att_bf16_d, ld_att, &ds)
+                : flash_bwd<ElemF32>(qkv_d, key_mask_d, att_d, datt_d, lse_d, dqkv_d, nullptr, 0, ws_d, batch, heads, t, as_stream(stream), qkv_staged,
+                                     att_d ? nullptr : (const uint16_t *)att_bf16_d, ld_att, &ds);
 }
 
 }  // extern "C"

@@ -27,6 +27,11 @@ class GPT2Config:
     n_pos: int = 1024
     ln_eps: float = 1e-5
     initializer_range: float = 0.02
+    # dropout rates of HF GPT2Config.  Carried, never applied implicitly: a train model drops only with the rates given to
+    # `train.gpt2_f32.GPT2F32(..., embd_pdrop=, attn_pdrop=, resid_pdrop=)` and a key given to its forward
+    embd_pdrop: float = 0.0
+    attn_pdrop: float = 0.0
+    resid_pdrop: float = 0.0
 
     @property
     def vocab_padded(self) -> int:

@@ -61,6 +61,28 @@ def split(key: Key, num: int = 2) -> List[Key]:
     return [(w[2 * i], w[2 * i + 1]) for i in range(num)]
 
 
+def as_key(key) -> Key:
+    """A key given as a `Key` (two uint32 words) or as an int seed (`prng_key(seed)`), the two forms the train steps accept."""
+    if isinstance(key, (tuple, list)) or (hasattr(key, "__len__") and len(key) == 2):
+        return (int(key[0]) & _M, int(key[1]) & _M)
+    return prng_key(int(key))
+
+
+class StepKeys:
+    """The key walk of a reference `_step`: `prng_key, new_key = jax.random.split(prng_key)` before every model call and every head call
+    (ilql/gpt2/interface.py:132-264 and its twins); `next()` returns `new_key` and carries the other half.  Built on None (the step got no
+    key, or runs with train=False) every `next()` is None."""
+
+    def __init__(self, key=None):
+        self.key = None if key is None else as_key(key)
+
+    def next(self):
+        if self.key is None:
+            return None
+        self.key, new_key = split(self.key)
+        return new_key
+
+
 def key_to_seed(key: Key) -> int:
     """The 64-bit `lmrl_sample_params.seed` carrying a key: (key[0] << 32) | key[1]."""
     return ((key[0] & _M) << 32) | (key[1] & _M)

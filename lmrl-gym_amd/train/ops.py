@@ -552,3 +552,57 @@ def flash_attn_bwd_staged(mm, qkv, key_mask, att, datt, lse, ws, batch, heads, t
     _lib.check(_L().lmrl_flash_attn_bwd_staged(_lib.ptr(qkv), _lib.ptr(key_mask), att.data_ptr(), datt.data_ptr(), lse.data_ptr(), dst.data_ptr(), ldb,
                                                ws.data_ptr(), batch, heads, t, int(qkv_staged), _sp()), "lmrl_flash_attn_bwd_staged")
     return dst
+
+
+# ---------------------------------------------------------------------- dropout (csrc/dropout.h: counter-based keep masks, never stored)
+def dropout_site_embd() -> int:
+    return 0
+
+
+def dropout_site_attn(layer: int) -> int:
+    return 1 + 3 * layer
+
+
+def dropout_site_attn_proj(layer: int) -> int:
+    return 2 + 3 * layer
+
+
+def dropout_site_mlp_proj(layer: int) -> int:
+    return 3 + 3 * layer
+
+
+def dropout_host_mask(key, site: int, n: int, p: float):
+    """Keep mask (numpy uint8 [n]) of one site, computed on the host by the library: the CPU tier's check of the device stream."""
+    import numpy as np
+    out = np.empty(max(int(n), 0), dtype=np.uint8)
+    _lib.check(_L().lmrl_dropout_host_mask(int(key[0]), int(key[1]), int(site), int(n), float(p), out.ctypes.data), "lmrl_dropout_host_mask")
+    return out
+
+
+def dropout_apply(x, y, key, site: int, p: float):
+    """y = x * mask / (1 - p) over the contiguous fp32 tensor x (y may be x): forward in place, backward on dy with the same (key, site, p)."""
+    assert x.is_contiguous() and y.is_contiguous() and x.numel() == y.numel()
+    _lib.check(_L().lmrl_dropout_apply(x.data_ptr(), y.data_ptr(), x.numel(), int(key[0]), int(key[1]), int(site), float(p), _sp()), "lmrl_dropout_apply")
+
+
+def dropout_apply_staged(mm: "MatmulBF16", x, rows, cols, key, site: int, p: float, name: str = "dy"):
+    """bf16-matmul mode: x * mask / (1 - p) written only as the bf16 dy operand of the next `linear_bwd(dyb=...)`."""
+    dst, ldb = mm._buf(name, _padn(rows) * _pitch(cols)), _pitch(cols)
+    _lib.check(_L().lmrl_dropout_apply_bf16(x.data_ptr(), rows, cols, dst.data_ptr(), ldb, _padn(rows), int(key[0]), int(key[1]), int(site), float(p), _sp()),
+               "lmrl_dropout_apply_bf16")
+    return dst
+
+
+def flash_attn_fwd_dropout(qkv, key_mask, att, lse, ws, att_b, ldb, batch, heads, t, bf16, key, site: int, p: float):
+    """The flash forward with dropout on the probabilities; argument forms of `flash_attn_fwd` / `flash_attn_fwd_staged`."""
+    _lib.check(_L().lmrl_flash_attn_fwd_dropout(_lib.ptr(qkv), _lib.ptr(key_mask), _lib.ptr(att), lse.data_ptr(), ws.data_ptr(), _lib.ptr(att_b), ldb, batch, heads,
+                                                t, int(bf16), int(key[0]), int(key[1]), int(site), float(p), _sp()), "lmrl_flash_attn_fwd_dropout")
+
+
+def flash_attn_bwd_dropout(mm, qkv, key_mask, att, attb, ld_attb, datt, lse, dqkv, ws, batch, heads, t, key, site: int, p: float, qkv_staged=True):
+    """The flash backward with dropout.  mm None: fp32 sweeps into `dqkv`; else the bf16 sweeps, d(qkv) returned as the staged bf16 dy operand."""
+    dst, ldb = (None, 0) if mm is None else mm.stage_dy(batch * t, 3 * heads * 64)
+    _lib.check(_L().lmrl_flash_attn_bwd_dropout(_lib.ptr(qkv), _lib.ptr(key_mask), _lib.ptr(att), _lib.ptr(attb), ld_attb, datt.data_ptr(), lse.data_ptr(),
+                                                _lib.ptr(dqkv) if mm is None else None, _lib.ptr(dst), ldb, ws.data_ptr(), batch, heads, t, int(mm is not None),
+                                                int(qkv_staged), int(key[0]), int(key[1]), int(site), float(p), _sp()), "lmrl_flash_attn_bwd_dropout")
+    return dst

@@ -59,6 +59,18 @@ def _add(ap: argparse.ArgumentParser, defaults: dict):
             ap.add_argument(flag, type=type(v), default=v)
 
 
+def _pdrop(a) -> dict:
+    """The GPT2F32 dropout rates of --embd-pdrop / --attn-pdrop / --resid-pdrop (default 0.0 each: no dropout launch anywhere)."""
+    return dict(embd_pdrop=a.embd_pdrop, attn_pdrop=a.attn_pdrop, resid_pdrop=a.resid_pdrop)
+
+
+def _step_keys(a):
+    """One dropout key per train step: `--seed` -> jax_prng.prng_key, split once per step (the reference train loops' `prng_key, new_key = split`);
+    every key is None while all three rates are 0, so the steps run exactly as they do without the flags."""
+    from lmrl_gym_amd import jax_prng
+    return jax_prng.StepKeys(jax_prng.prng_key(a.seed) if max(_pdrop(a).values()) > 0 else None)
+
+
 def _tokenizer(wordle: bool = True):
     from lmrl_gym_amd.datasets import ByteTokenizer, WordleTokenizer
     try:
@@ -164,8 +176,9 @@ def cmd_ilql(a):
     tok = _tokenizer()
     cfg, sd = _model(a.model, max(len(tok), 50257))
     mm = dict(matmul="bf16" if a.bf16_activations else "f32")                 # the scripts' bf16_activations / gradient_checkpointing flags
-    base = GPT2F32(sd, cfg.n_head, device=dev, gradient_checkpointing=a.gradient_checkpointing, **mm)
-    target_base, pi_beta = GPT2F32(sd, cfg.n_head, device=dev, **mm), _engine(cfg, sd, a.policy_engine)
+    base = GPT2F32(sd, cfg.n_head, device=dev, gradient_checkpointing=a.gradient_checkpointing, **mm, **_pdrop(a))
+    # (the reference calls the target network with train=train too: it drops with its own key, ilql/gpt2/interface.py:149-161)
+    target_base, pi_beta = GPT2F32(sd, cfg.n_head, device=dev, **mm, **_pdrop(a)), _engine(cfg, sd, a.policy_engine)
     d, V = cfg.d_model, cfg.vocab
     g = torch.Generator().manual_seed(0)
     # MLPHead init of train_ilql_gpt2.py:224-231: layer-2 kernel 0, layer-2 bias -4.4 (Q heads) ; V head likewise
@@ -211,14 +224,14 @@ def cmd_ilql(a):
         _, summary = E.text_env_eval(env, pol, n_rollouts=a.policy_n_rollouts, bsize=a.policy_bsize, seed_generator=iter(range(10 ** 9)), verbose=False)
         return summary
 
-    step = 0
+    step, keys = 0, _step_keys(a)
     for epoch in range(a.epochs):
         for batch in batches(epoch):
             if a.device_data:
-                _, loss, logs = tr.step(**batch)
+                _, loss, logs = tr.step(**batch, prng_key=keys.next())
             else:
                 _, loss, logs = tr.step(batch["input_ids"], batch["should_take_action"], batch["rewards"], batch["dones"],
-                                        next_token_ids=batch["next_token_ids"], next_dones=batch["next_dones"])
+                                        next_token_ids=batch["next_token_ids"], next_dones=batch["next_dones"], prng_key=keys.next())
             step += 1
             if step % a.log_every == 0 or step == 1:
                 _log("train", dict(step=step, epoch=epoch, loss=loss, losses=logs["losses"]))
@@ -247,7 +260,8 @@ def cmd_ppo(a):
     tok = _tokenizer(wordle=a.env == "wordle")       # FEN / SAN text needs every byte: the byte tokenizer when no GPT-2 files are around
     cfg, sd = _model(a.model, max(len(tok), 50257))
     mm = dict(matmul="bf16" if a.bf16_activations else "f32")
-    pol_f32 = GPT2F32(sd, cfg.n_head, device=dev, gradient_checkpointing=a.gradient_checkpointing, **mm)
+    pol_f32 = GPT2F32(sd, cfg.n_head, device=dev, gradient_checkpointing=a.gradient_checkpointing, **mm, **_pdrop(a))
+    keys = _step_keys(a)
     init_f32 = GPT2F32(sd, cfg.n_head, device=dev, **mm)
     head = LinearHeadF32(dict(kernel=torch.zeros(cfg.d_model, 1), bias=torch.tensor([-4.1])), dev)       # train_ppo_gpt2.py:254-260
     kw = dict(cliprange_value=a.cliprange_value, cliprange=a.cliprange, value_loss_coef=a.value_loss_coef)
@@ -321,7 +335,7 @@ def cmd_ppo(a):
                             bc_iter = DS.dataloader(np.random.default_rng(7 + step), bc, int(a.train_bc_bsize or a.train_bsize), truncate=True)
                             bb = next(bc_iter)
                         extra = dict(bc_data_input_ids=bb["input_ids"], bc_data_input_training_mask=bb["input_training_mask"])
-                    _, loss, logs = tr.step(**batch, **extra)
+                    _, loss, logs = tr.step(**batch, **extra, prng_key=keys.next())
                     step += 1
                     _log("train", dict(step=step, round=rnd, loss=loss))
                     if limit is not None and step >= limit:
@@ -373,7 +387,7 @@ def cmd_ppo(a):
                         bc_iter = DS.dataloader(np.random.default_rng(7 + step), bc, int(a.train_bc_bsize or a.train_bsize), truncate=True)
                         bb = next(bc_iter)
                     extra = dict(bc_data_input_ids=bb["input_ids"], bc_data_input_training_mask=bb["input_training_mask"])
-                _, loss, logs = tr.step(**batch, **extra)
+                _, loss, logs = tr.step(**batch, **extra, prng_key=keys.next())
                 step += 1
                 _log("train", dict(step=step, round=rnd, loss=loss))
                 if a.max_steps is not None and step >= int(a.max_steps):
@@ -395,7 +409,8 @@ def cmd_filtered_bc(a):
     dev = _lib.require_gpu()
     tok = _tokenizer()
     cfg, sd = _model(a.model, max(len(tok), 50257))
-    model = GPT2F32(sd, cfg.n_head, device=dev, matmul="bf16" if a.bf16_activations else "f32", gradient_checkpointing=a.gradient_checkpointing)
+    model = GPT2F32(sd, cfg.n_head, device=dev, matmul="bf16" if a.bf16_activations else "f32", gradient_checkpointing=a.gradient_checkpointing, **_pdrop(a))
+    keys = _step_keys(a)
     tr = bc.GPT2BCTrain(model, tok.pad_token_id, lr=a.lr, weight_decay=a.weight_decay, grad_accum_steps=int(a.grad_accum_steps or 1))
     policy = GPT2PPOPolicy(_engine(cfg, sd), tok, max_input_length=a.max_input_length, max_new_tokens=a.max_output_length, do_sample=a.policy_do_sample,
                            temperature=a.policy_temperature, top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p,
@@ -428,7 +443,7 @@ def cmd_filtered_bc(a):
                 if limit is not None and step >= limit:
                     break
                 for batch in ds.batches(np.random.default_rng(rnd * 1000 + epoch), min(a.train_bsize, len(ds)), truncate=True):
-                    _, loss, _ = tr.step(**batch)
+                    _, loss, _ = tr.step(**batch, prng_key=keys.next())
                     step += 1
                     _log("train", dict(step=step, round=rnd, loss=loss))
                     if limit is not None and step >= limit:
@@ -462,7 +477,7 @@ def cmd_filtered_bc(a):
             if limit is not None and step >= limit:
                 break
             for batch in DS.dataloader(np.random.default_rng(rnd * 1000 + epoch), ds, min(a.train_bsize, len(ds)), truncate=True):
-                _, loss, _ = tr.step(batch["input_ids"], batch["input_training_mask"] > 0)
+                _, loss, _ = tr.step(batch["input_ids"], batch["input_training_mask"] > 0, prng_key=keys.next())
                 step += 1
                 _log("train", dict(step=step, round=rnd, loss=loss))
                 if limit is not None and step >= limit:
@@ -525,6 +540,14 @@ def build_parser() -> argparse.ArgumentParser:
         p.add_argument("--rollout-lanes", type=int, default=1, help="device rollouts: independent episode batches in flight at once "
                                                                      "(WordleRolloutEngine.text_env_eval(concurrent=n); >= 4 batches use the graph path)")
         _add(p, defaults)
+    for name in ("ilql", "filtered-bc", "ppo"):
+        p = sub.choices[name]
+        for site in ("resid", "attn", "embd"):
+            p.add_argument(f"--{site}-pdrop", type=float, default=0.0,
+                           help=f"GPT-2 {site}_pdrop of the train model (default 0.0 = no dropout).  The reference's values: BC 0.05 on all three "
+                                "(train_bc_gpt2.py), ILQL and MC 0.1 on all three (the HF GPT2Config default, which its scripts leave alone), PPO and online "
+                                "filtered BC 0.0")
+        p.add_argument("--seed", type=int, default=0, help="seed of the dropout key (jax_prng.prng_key(seed), split once per train step)")
     sub.choices["ilql"].add_argument("--train-data", default=None)
     for name in ("ilql", "filtered-bc"):
         sub.choices[name].add_argument("--device-data", type=int, default=0,

@@ -1200,6 +1200,48 @@ int lmrl_mc_loss_nstats(void);
 int lmrl_mc_loss(const float *q_d, const float *ce_d, const float *attn_d, const uint8_t *sta_d, const float *returns_d, size_t n,
                  float cql_weight, const double *n_mask_d, double *partials_d, float *dq_d, float *coef_ce_d, void *stream);
 
+/* ---- beam search on the device (csrc/beam.hip; the rules of HF-Flax `_beam_search`, transformers 4.26.1, restated in DESIGN.md "Beam search" and
+ * unverified against the library).  Per batch item K = num_beams running beams and a pool of K finished hypotheses; rows are item * K + beam.
+ * Every buffer is the caller's.  The -1e7 penalties of the rules are carried as flags, never added into a stored value, except in run_score
+ * (a beam that was never alive holds -1e7, as the rules initialise it): an UNFLAGGED pool entry stands for fin_score - 1e7.
+ * ctl_d: int32 [4][max_new_tokens + 1], zeroed, then ctl[0][0] = 1.  Row 0 is go[t]: position t runs; written for t + 1 by lmrl_beam_select
+ * of position t (the loop condition is global over the batch).  Rows 1 - 3 are scratch of lmrl_beam_select.  Every entry below returns at once
+ * when its go word is 0, so steps enqueued past the stopping point change nothing. */
+typedef struct {
+    float *run_score;     /* [b K]      sum of log-probabilities of the running beams, descending per item; initially {0, -1e7, ...} */
+    int32_t *run_hist;    /* [b K][cap] their generated tokens */
+    float *fin_score;     /* [b K]      finished pool: score / length ** length_penalty (unpenalised); initially 0 */
+    uint8_t *fin_flag;    /* [b K]      1: a hypothesis that ended in eos; initially 0 */
+    int32_t *fin_hist;    /* [b K][cap] tokens of the pool entries, pad_token behind the last */
+} lmrl_beam_state;
+/* One workgroup per row, one pass over logits_d [rows][ld] (ld % 4 == 0, 16-byte aligned) with 16-byte loads: log-sum-exp over columns [0, vocab)
+ * and the row's n_cand (<= min(32, vocab)) largest logits there, ties to the lower column -> cand_score_d [rows][n_cand] = logit - lse +
+ * running_score_d[row] in descending order, cand_tok_d [rows][n_cand] their columns.  Columns >= vocab are never looked at.  active_d (NULL: all):
+ * rows with 0 are skipped; go_d (NULL: run): one word. */
+int lmrl_beam_row_topk(const float *logits_d, int ld, int rows, int vocab, int n_cand, const float *running_score_d, const uint8_t *active_d,
+                       const int32_t *go_d, float *cand_score_d, int32_t *cand_tok_d, void *stream);
+/* One wave per item, position t (0-based) of the generation: with the candidates of lmrl_beam_row_topk at n_cand = 2 num_beams (num_beams <= 16,
+ * vocab >= 2 num_beams) — the item's top 2K by score (ties: lower beam * vocab + token); the next running beams = those candidates in rank order,
+ * eos candidates behind all others; the finished pool = top K of [pool | candidates] by (unpenalised first, score / norm_div, lower merged
+ * index), candidates penalised unless they end in eos_token (< 0: none), all of them when the pool was full and early_stopping is set.  `in` is
+ * read, `out` written (two states, no shared buffer).  parent_d [b K]: absolute row whose cache each new running beam continues; next_tok_d /
+ * next_cnt_d [b K]: the inputs of the next single-token forward (next_cnt_d = 1; all 0 once go[t + 1] is 0).  norm_div = (prompt width + t) **
+ * length_penalty, best_div = (prompt width + max_new_tokens) ** length_penalty: go[t + 1] = t + 1 < max_new_tokens, and not (every pool of the
+ * batch full and early_stopping), and some item has a beam whose worst_finished (the pool's minimum where the beam's entry is flagged, -1e7
+ * elsewhere) lies below run_score[best_running_beam] / best_div. */
+int lmrl_beam_select(const lmrl_beam_state *in, const lmrl_beam_state *out, const float *cand_score_d, const int32_t *cand_tok_d, int32_t *parent_d,
+                     int32_t *next_tok_d, int32_t *next_cnt_d, int32_t *ctl_d, int b, int num_beams, int vocab, int cap, int t, int max_new_tokens,
+                     int eos_token, int pad_token, int early_stopping, int best_running_beam, float norm_div, float best_div, void *stream);
+/* The caches follow the beams: for every layer, K and V of positions [from_d[i] (NULL: 0), src_len_d[parent_d[i]]) of source row parent_d[i] go to
+ * row i of a SECOND cache of the same shape (b rows of tmax positions), dst_len_d[i] = src_len_d[parent_d[i]], and the last hidden state (the fp32
+ * form: and the last residual) is copied.  from_d = pfx_n_d of the attach call: the prompt's rows stay where they are.  One launch for all layers. */
+int lmrl_gpt2_kv_reorder(const lmrl_gpt2 *m, const void *src_kv_d, const int32_t *src_len_d, const void *src_hidden_d, const int32_t *parent_d,
+                         const int32_t *from_d, void *dst_kv_d, int32_t *dst_len_d, void *dst_hidden_d, int b, int tmax, const int32_t *go_d,
+                         void *stream);
+int lmrl_kv_reorder_f32(const float *src_kv_d, const int32_t *src_len_d, const float *src_hidden_d, const float *src_last_x_d, const int32_t *parent_d,
+                        const int32_t *from_d, float *dst_kv_d, int32_t *dst_len_d, float *dst_hidden_d, float *dst_last_x_d, int b, int tmax, int n_layer,
+                        int d, const int32_t *go_d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

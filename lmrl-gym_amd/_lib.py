@@ -249,6 +249,10 @@ _SIGS = {
     "lmrl_mc_loss": (c_int, [c_void_p] * 5 + [c_size_t, c_float] + [c_void_p] * 5),
     "lmrl_gen_accept": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "lmrl_sample_logits": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lmrl_beam_row_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lmrl_beam_select": (c_int, [c_void_p] * 8 + [c_int] * 10 + [c_float, c_float, c_void_p]),
+    "lmrl_gpt2_kv_reorder": (c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p]),
+    "lmrl_kv_reorder_f32": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 

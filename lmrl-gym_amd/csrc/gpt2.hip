@@ -972,6 +972,31 @@ __global__ __launch_bounds__(1024) void kv_attach_kernel(int src_b, const int32_
     }
 }
 
+// Beam search (lmrl_gpt2_kv_reorder): row i of the destination cache continues source row parent[i] — K and V of the GENERATED positions
+// [from[i], src_len[parent[i]]) of every layer, the cache length and the last hidden state.  Positions below from[i] (the attached prompt
+// prefix, pfx_n_d of lmrl_gpt2_kv_attach) belong to the prefix session and are not touched.  Out of place: two caches of one shape.
+// One workgroup per (row, layer x K|V), 16 B per lane.  *go == 0: nothing is written.
+__global__ __launch_bounds__(256) void kv_reorder_kernel(const uint16_t *__restrict__ src, const int32_t *__restrict__ src_len,
+                                                         const int32_t *__restrict__ parent, const int32_t *__restrict__ from,
+                                                         uint16_t *__restrict__ dst, int32_t *__restrict__ dst_len, int B, int tmax, int d,
+                                                         const uint16_t *__restrict__ src_hidden, uint16_t *__restrict__ dst_hidden,
+                                                         const int32_t *__restrict__ go) {
+    if (go && *go == 0) return;
+    const int b = blockIdx.x, lk = blockIdx.y;
+    const int r = parent[b];
+    if (r < 0 || r >= B) return;
+    const int hi = min(src_len[r], tmax), lo = min(max(from ? from[b] : 0, 0), hi);
+    const u32x4 *sp = reinterpret_cast<const u32x4 *>(src + (((size_t)lk * B + r) * tmax + lo) * d);
+    u32x4 *dp = reinterpret_cast<u32x4 *>(dst + (((size_t)lk * B + b) * tmax + lo) * d);
+    const int chunks = (hi - lo) * (d / 8);
+    for (int i = threadIdx.x; i < chunks; i += blockDim.x) dp[i] = sp[i];
+    if (lk == 0) {
+        if (dst_hidden) for (int i = threadIdx.x; i < d / 8; i += blockDim.x)
+            reinterpret_cast<u32x4 *>(dst_hidden + (size_t)b * d)[i] = reinterpret_cast<const u32x4 *>(src_hidden + (size_t)r * d)[i];
+        if (threadIdx.x == 0) dst_len[b] = hi;
+    }
+}
+
 // profiling only (one launch per forward): algorithmic HBM bytes of the attention launches of this forward =
 // per (env, head, layer): K and V rows of every attended position (2 x 128 B) + the chunk's q rows and output rows.
 __global__ void attn_bytes_kernel(const int32_t *cnt, const int32_t *len, int B, int C, int heads_x_layers,
@@ -1470,6 +1495,18 @@ int lmrl_gpt2_kv_gather(const lmrl_gpt2 *m, const void *src_kv_d, int src_b, int
     hipLaunchKernelGGL(kv_gather_kernel, dim3(b, 2 * m->cfg.n_layer), dim3(256), 0, as_stream(stream), (const uint16_t *)src_kv_d, src_b, src_tmax,
                        src_len_d, idx_d, (uint16_t *)dst_kv_d, dst_tmax, b, m->cfg.d_model, (const uint16_t *)src_hidden_d, (uint16_t *)dst_hidden_d,
                        dst_len_d);
+    LMRL_CHECK_LAUNCH();
+    return LMRL_OK;
+}
+
+int lmrl_gpt2_kv_reorder(const lmrl_gpt2 *m, const void *src_kv_d, const int32_t *src_len_d, const void *src_hidden_d, const int32_t *parent_d,
+                         const int32_t *from_d, void *dst_kv_d, int32_t *dst_len_d, void *dst_hidden_d, int b, int tmax, const int32_t *go_d,
+                         void *stream) {
+    LMRL_REQUIRE(m && src_kv_d && src_len_d && parent_d && dst_kv_d && dst_len_d && b > 0 && tmax > 0, "lmrl_gpt2_kv_reorder: bad argument");
+    LMRL_REQUIRE(src_kv_d != dst_kv_d && src_len_d != dst_len_d, "lmrl_gpt2_kv_reorder: the copy is out of place (two caches of one shape)");
+    LMRL_REQUIRE(!dst_hidden_d || src_hidden_d, "lmrl_gpt2_kv_reorder: dst_hidden_d needs src_hidden_d");
+    hipLaunchKernelGGL(kv_reorder_kernel, dim3(b, 2 * m->cfg.n_layer), dim3(256), 0, as_stream(stream), (const uint16_t *)src_kv_d, src_len_d, parent_d,
+                       from_d, (uint16_t *)dst_kv_d, dst_len_d, b, tmax, m->cfg.d_model, (const uint16_t *)src_hidden_d, (uint16_t *)dst_hidden_d, go_d);
     LMRL_CHECK_LAUNCH();
     return LMRL_OK;
 }

@@ -94,6 +94,31 @@ __global__ __launch_bounds__(1024) void kv_attach_f32_kernel(int src_b, int src_
     }
 }
 
+// Beam search (lmrl_kv_reorder_f32, the fp32 twin of gpt2.hip's kv_reorder_kernel): row i of the destination cache continues source row
+// parent[i] — K and V of the generated positions [from[i], src_len[parent[i]]) of every layer, the cache length, the last hidden state and the
+// last residual.  Positions below from[i] (the attached prompt prefix) are not touched.  Out of place; *go == 0: nothing is written.
+__global__ __launch_bounds__(256) void kv_reorder_f32_kernel(const float *__restrict__ src, const int32_t *__restrict__ src_len, const int32_t *__restrict__ parent,
+                                                             const int32_t *__restrict__ from, float *__restrict__ dst, int32_t *__restrict__ dst_len, int B,
+                                                             int tmax, int d, const float *__restrict__ src_hidden, const float *__restrict__ src_last_x,
+                                                             float *__restrict__ dst_hidden, float *__restrict__ dst_last_x, const int32_t *__restrict__ go) {
+    if (go && *go == 0) return;
+    const int b = blockIdx.x, lk = blockIdx.y;
+    const int r = parent[b];
+    if (r < 0 || r >= B) return;
+    const int hi = min(src_len[r], tmax), lo = min(max(from ? from[b] : 0, 0), hi);
+    const float4 *sp = reinterpret_cast<const float4 *>(src + (((size_t)lk * B + r) * tmax + lo) * d);
+    float4 *dp = reinterpret_cast<float4 *>(dst + (((size_t)lk * B + b) * tmax + lo) * d);
+    const int chunks = (hi - lo) * (d / 4);
+    for (int i = threadIdx.x; i < chunks; i += blockDim.x) dp[i] = sp[i];
+    if (lk == 0) {
+        for (int i = threadIdx.x; i < d / 4; i += blockDim.x) {
+            if (dst_hidden) reinterpret_cast<float4 *>(dst_hidden + (size_t)b * d)[i] = reinterpret_cast<const float4 *>(src_hidden + (size_t)r * d)[i];
+            if (dst_last_x) reinterpret_cast<float4 *>(dst_last_x + (size_t)b * d)[i] = reinterpret_cast<const float4 *>(src_last_x + (size_t)r * d)[i];
+        }
+        if (threadIdx.x == 0) dst_len[b] = hi;
+    }
+}
+
 }  // namespace lmrl
 
 using namespace lmrl;
@@ -120,6 +145,19 @@ int lmrl_kv_attach_f32(int src_b, int src_tmax, const int32_t *src_len_d, const 
     LMRL_REQUIRE((!dst_hidden_d || src_hidden_d) && (!dst_last_x_d || src_last_x_d), "lmrl_kv_attach_f32: a destination row without its source");
     hipLaunchKernelGGL(kv_attach_f32_kernel, dim3(b + 1), dim3(1024), 0, as_stream(stream), src_b, src_tmax, src_len_d, idx_d, b, d, dst_tmax,
                        src_hidden_d, src_last_x_d, dst_hidden_d, dst_last_x_d, dst_len_d, pfx_n_d, order_d);
+    LMRL_CHECK_LAUNCH();
+    return LMRL_OK;
+}
+
+int lmrl_kv_reorder_f32(const float *src_kv_d, const int32_t *src_len_d, const float *src_hidden_d, const float *src_last_x_d, const int32_t *parent_d,
+                        const int32_t *from_d, float *dst_kv_d, int32_t *dst_len_d, float *dst_hidden_d, float *dst_last_x_d, int b, int tmax, int n_layer,
+                        int d, const int32_t *go_d, void *stream) {
+    LMRL_REQUIRE(src_kv_d && src_len_d && parent_d && dst_kv_d && dst_len_d && b > 0 && tmax > 0 && n_layer > 0 && d > 0 && d % 4 == 0,
+                 "lmrl_kv_reorder_f32: bad argument");
+    LMRL_REQUIRE(src_kv_d != dst_kv_d && src_len_d != dst_len_d, "lmrl_kv_reorder_f32: the copy is out of place (two caches of one shape)");
+    LMRL_REQUIRE((!dst_hidden_d || src_hidden_d) && (!dst_last_x_d || src_last_x_d), "lmrl_kv_reorder_f32: a destination row without its source");
+    hipLaunchKernelGGL(kv_reorder_f32_kernel, dim3(b, 2 * n_layer), dim3(256), 0, as_stream(stream), src_kv_d, src_len_d, parent_d, from_d, dst_kv_d, dst_len_d,
+                       b, tmax, d, src_hidden_d, src_last_x_d, dst_hidden_d, dst_last_x_d, go_d);
     LMRL_CHECK_LAUNCH();
     return LMRL_OK;
 }

@@ -73,13 +73,23 @@ class GPT2PPOPolicy(BatchedTextPolicy):
                  temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, seed: int = 0, in_str_process: Optional[Callable[[str], str]] = None,
-                 out_str_process: Optional[Callable[[str], str]] = None, reuse_kv: bool = True, sampler: str = "philox"):
-        """sampler: "philox" (default) — the package's counter-based stream, keyed by (seed, act() call, row, column, token position);
+                 out_str_process: Optional[Callable[[str], str]] = None, reuse_kv: bool = True, sampler: str = "philox",
+                 num_beams: int = 1, length_penalty: float = 1.0, early_stopping: bool = False):
+        """num_beams > 1 (with do_sample=False): beam search on the device (`lmrl_gym_amd.beam.BeamSearch`; HF-Flax `_beam_search` of transformers
+        4.26.1 as restated in DESIGN.md "Beam search", unverified against the library) with `length_penalty` / `early_stopping` of `GenerationConfig`;
+        temperature / top_k / top_p do not apply there.  num_beams > 1 with do_sample=True raises NotImplementedError, as the library does.
+        sampler: "philox" (default) — the package's counter-based stream, keyed by (seed, act() call, row, column, token position);
         "jax" — the reference's stream: `seed` is the integer of `jax.random.PRNGKey(seed)` handed to the policy, split once per act()
         (ppo/gpt2/interface.py:524-526) and once per generated token (HF-Flax `_sample`), each token drawn as
         `jax.random.categorical(key, logits[B, V])` (lmrl_gym_amd/jax_prng.py + csrc/threefry.h; restated from jax 0.4.7's published
         algorithm, unverified against jax itself)."""
         assert sampler in ("philox", "jax")
+        if int(num_beams) < 1:
+            raise ValueError(f"num_beams = {num_beams}")
+        if num_beams > 1 and do_sample:
+            raise NotImplementedError("Beam sampling is currently not implemented.")
+        self.num_beams, self.length_penalty, self.early_stopping = int(num_beams), float(length_penalty), bool(early_stopping)
+        self._beam = None
         self.engine, self.tokenizer = engine, tokenizer
         self.sampler = sampler
         self.prng_key = jax_prng.prng_key(seed)
@@ -98,6 +108,9 @@ class GPT2PPOPolicy(BatchedTextPolicy):
     # hooks the ILQL policy overrides
     def _engines(self) -> List[GPT2Engine]:
         return [self.engine]
+
+    def _q_heads(self):
+        return None, 0.0
 
     def _sample(self, gen: _Generator, params: SampleParams, active_d, logits_out):
         return gen.sessions[0].sample(params, active=active_d, logits_out=logits_out, want_logprob=False)
@@ -122,10 +135,25 @@ class GPT2PPOPolicy(BatchedTextPolicy):
                 ids = memo[s] = ids if ids else [self.pad]
             prompts.append(ids)
         tmax = -(-(self.max_input_length + self.max_new_tokens + 16) // 16) * 16
+        if self.num_beams > 1:
+            return self._act_beam(prompts, text_history, done, B, tmax)
         if self._gen is None or self._gen.B != B or self._gen.tmax != tmax:
             self._gen = _Generator(self._engines(), B, tmax)
         gen = self._gen
         return self._generate(gen, prompts, text_history, done, B)
+
+    def _act_beam(self, prompts, text_history, done, B, tmax):
+        from .beam import BeamSearch
+        if self._beam is None or self._beam.B != B or self._beam.tmax != tmax:
+            heads, beta = self._q_heads()
+            self._beam = BeamSearch(self._engines(), B, self.num_beams, tmax, q_heads=heads, beta=beta, length_penalty=self.length_penalty,
+                                    early_stopping=self.early_stopping, eos_token_id=self.eos, pad_token_id=self.pad)
+        # the scripts' BlockingStrategy(Padding.LEFT, Truncation.LEFT, max_length=max_input_length) pads every prompt to max_input_length: that
+        # width, not the prompt's own length, enters the length normalisation
+        seqs, _ = self._beam.run(prompts, self.max_new_tokens, prompt_width=self.max_input_length, reuse=self.reuse_kv)
+        self.calls += 1
+        return [None if d else tuple(h) + (Text(self.out_str_process(self._decode_generation(ids)), True),)
+                for h, d, ids in zip(text_history, done, seqs)]
 
     def _generate(self, gen, prompts, text_history, done, B):
         import torch
@@ -189,7 +217,7 @@ class GPT2PPOPolicy(BatchedTextPolicy):
     def set_params(self, engine: GPT2Engine) -> None:
         """PPOPolicy.set_params (ppo/base_interface.py:821-823): swap in freshly trained weights."""
         self.engine = engine
-        self._gen = None
+        self._gen = self._beam = None
 
 
 class GPT2ValuePolicy(GPT2PPOPolicy):
@@ -213,7 +241,10 @@ class GPT2ValuePolicy(GPT2PPOPolicy):
         pi_beta, base, q1, q2 = policy_params
         check_value_policy(pi_beta, base, (q1, q2))
         self.engine, self.value_base, self.q1, self.q2 = pi_beta, base, q1, q2
-        self._gen = None
+        self._gen = self._beam = None
+
+    def _q_heads(self):
+        return (self.q1, self.q2), self.beta
 
     def _sample(self, gen, params, active_d, logits_out):
         pi_ses, v_ses = gen.sessions

@@ -30,20 +30,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 ILQL_DEFAULTS = dict(epochs=10, max_steps=None, lr=3e-5, weight_decay=0.0, train_bsize=32, grad_accum_steps=1, max_length=512, log_every=256,
                      policy_max_input_length=256, policy_max_output_length=256, policy_do_sample=True, policy_temperature=None,
-                     policy_top_p=None, policy_top_k=None, policy_bsize=32, policy_n_rollouts=32, beta=32.0, polyak_alpha=0.005,
+                     policy_top_p=None, policy_top_k=None, policy_num_beams=1, policy_bsize=32, policy_n_rollouts=32, beta=32.0, polyak_alpha=0.005,
                      hard_update_every=None, gamma=0.99, tau=0.7, cql_weight=0.01, bad_word_reward=-10.0,
                      bf16_activations=False, gradient_checkpointing=False)                                   # train_ilql_gpt2.py:41-117, :369
 PPO_DEFAULTS = dict(n_rounds=1, epochs=1, max_steps=None, lr=1e-5, weight_decay=0.0, train_bsize=32, train_bc_bsize=None, grad_accum_steps=None,
                     rollout_bsize=32, n_rollouts=128, ppo_data_bsize=32, max_input_length=512, max_output_length=512, policy_do_sample=True,
-                    policy_temperature=None, policy_top_p=None, policy_top_k=None, gamma=1.0, lam=0.95, use_advantage_whitening=True,
+                    policy_temperature=None, policy_top_p=None, policy_top_k=None, policy_num_beams=1, gamma=1.0, lam=0.95, use_advantage_whitening=True,
                     init_kl_coef=0.001, kl_target=None, kl_horizon=None, cliprange_value=0.2, cliprange=0.2, value_loss_coef=1.0,
                     bc_loss_weight=1.0, bad_word_reward=-10.0, bf16_activations=False, gradient_checkpointing=False)   # train_ppo_gpt2.py:40-112, :211
 FILTERED_BC_DEFAULTS = dict(n_rounds=1, epochs=1, max_steps=None, lr=1e-5, weight_decay=0.0, train_bsize=32, grad_accum_steps=None, rollout_bsize=32,
                             n_rollouts=128, filter_percengage=0.3, bf16_activations=False, gradient_checkpointing=False, max_input_length=512,
-                            max_output_length=512, policy_do_sample=True, policy_temperature=None, policy_top_p=None, policy_top_k=None,
+                            max_output_length=512, policy_do_sample=True, policy_temperature=None, policy_top_p=None, policy_top_k=None, policy_num_beams=1,
                             bad_word_reward=-10.0)                                    # wordle/online_filtered_bc/train_online_filtered_bc_gpt2.py:40-87
 BC_EVAL_DEFAULTS = dict(policy_n_rollouts=32, policy_bsize=1, policy_max_input_length=256, policy_max_output_length=256, policy_do_sample=True,
-                        policy_temperature=None, policy_top_p=None, policy_top_k=None)                         # eval_bc_gpt2.py
+                        policy_temperature=None, policy_top_p=None, policy_top_k=None, policy_num_beams=1)                         # eval_bc_gpt2.py
 MAZE_EVAL_DEFAULTS = dict(maze_name="double_t_maze", describe_function="describe_observation_only_walls", reward_function="standard_reward",
                           last_k=1, max_steps=100, generation_bsize=4, max_input_length=128, max_output_length=8)   # fully_observed_bc.py:230-283
 
@@ -219,7 +219,7 @@ def cmd_ilql(a):
             return summary
         pol = GPT2ValuePolicy(pi_beta, _engine(cfg, base.p, a.policy_engine), hl(tr.q1), hl(tr.q2), a.beta, tok, max_input_length=a.policy_max_input_length,
                               max_new_tokens=a.policy_max_output_length, do_sample=a.policy_do_sample, temperature=a.policy_temperature,
-                              top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p, eos_token_id=tok.encode("\n")[0],
+                              top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p, num_beams=a.policy_num_beams, eos_token_id=tok.encode("\n")[0],
                               out_str_process=lambda x: x.removesuffix("\n") + "\n")
         _, summary = E.text_env_eval(env, pol, n_rollouts=a.policy_n_rollouts, bsize=a.policy_bsize, seed_generator=iter(range(10 ** 9)), verbose=False)
         return summary
@@ -267,7 +267,7 @@ def cmd_ppo(a):
     kw = dict(cliprange_value=a.cliprange_value, cliprange=a.cliprange, value_loss_coef=a.value_loss_coef)
     max_len = a.max_input_length + a.max_output_length
     policy = GPT2PPOPolicy(_engine(cfg, sd), tok, max_input_length=a.max_input_length, max_new_tokens=a.max_output_length, do_sample=a.policy_do_sample,
-                           temperature=a.policy_temperature, top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p,
+                           temperature=a.policy_temperature, top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p, num_beams=a.policy_num_beams,
                            eos_token_id=tok.encode("\n")[0], out_str_process=lambda x: x.removesuffix("\n") + "\n")
     inf = GPT2PPOInference(pol_f32, head, tok.pad_token_id, initial_policy=init_f32, tokenizer=tok, loss_kwargs=kw, bc_loss_weight=a.bc_loss_weight)
     tr = ppo.GPT2PPOTrain(pol_f32, head, tok.pad_token_id, kw, lr=a.lr, weight_decay=a.weight_decay, grad_accum_steps=int(a.grad_accum_steps or 1),
@@ -413,7 +413,7 @@ def cmd_filtered_bc(a):
     keys = _step_keys(a)
     tr = bc.GPT2BCTrain(model, tok.pad_token_id, lr=a.lr, weight_decay=a.weight_decay, grad_accum_steps=int(a.grad_accum_steps or 1))
     policy = GPT2PPOPolicy(_engine(cfg, sd), tok, max_input_length=a.max_input_length, max_new_tokens=a.max_output_length, do_sample=a.policy_do_sample,
-                           temperature=a.policy_temperature, top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p,
+                           temperature=a.policy_temperature, top_k=None if a.policy_top_k is None else int(a.policy_top_k), top_p=a.policy_top_p, num_beams=a.policy_num_beams,
                            eos_token_id=tok.encode("\n")[0], out_str_process=lambda x: x.removesuffix("\n") + "\n")
     vocab, env = _wordle_env(a)
     bs = BlockingStrategy(Padding.RIGHT, Truncation.LEFT, a.max_input_length + a.max_output_length)
@@ -494,7 +494,7 @@ def cmd_bc_eval(a):
     cfg, sd = _model(a.model, max(len(tok), 50257))
     policy = GPT2PPOPolicy(_engine(cfg, sd), tok, max_input_length=a.policy_max_input_length, max_new_tokens=a.policy_max_output_length,
                            do_sample=a.policy_do_sample, temperature=a.policy_temperature, top_k=None if a.policy_top_k is None else int(a.policy_top_k),
-                           top_p=a.policy_top_p, eos_token_id=tok.encode("\n")[0], out_str_process=lambda x: x.removesuffix("\n") + "\n")
+                           top_p=a.policy_top_p, num_beams=a.policy_num_beams, eos_token_id=tok.encode("\n")[0], out_str_process=lambda x: x.removesuffix("\n") + "\n")
     vocab, env = _wordle_env(a)
     if a.device_rollouts:       # same call, env + policy + loop on the GPU
         ro = _device_rollouts(policy.engine, vocab, tok, a.policy_bsize, -1.0, min(a.policy_max_output_length, 12))
@@ -598,6 +598,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    if getattr(a, "policy_num_beams", 1) > 1 and getattr(a, "device_rollouts", 0):
+        # the device-resident rollout engines sample (temperature / top_k / top_p); beam search runs in the text policies' act() only
+        raise SystemExit("--policy-num-beams > 1 is not available with --device-rollouts 1 (the device rollout loops do not run beam search); "
+                         "use --device-rollouts 0")
     a.fn(a)
 
 

@@ -959,6 +959,124 @@ int lmrl_chess_host_action_from_tokens(const lmrl_chess_tok_ctx *c, const int32_
 uint32_t lmrl_chess_host_reply_word(uint64_t seed, uint32_t epoch, uint32_t turn, uint32_t env);
 
 /* ------------------------------------------------------------------------------------------
+ * On-device token <-> game bookkeeping for lock-step Twenty Questions rollouts (csrc/tq_tokens.hip; the text rules: csrc/tq_core.h): the twin of
+ * the loops above for `BatchedTwentyQuestionsPolicyEnvironment` + `GPT2EngineOracle` (twenty_questions/env/{env,data,oracle}.py; the PPO script
+ * twenty_questions/ppo/train_ppo.py), the env with TWO models in the loop.  A turn: guesser decode | lmrl_tq_question | oracle prefill
+ * (lmrl_tq_oracle_prompt per chunk) | <= oracle_max_new_tokens greedy steps | lmrl_tq_answer | lmrl_tq_judge | guesser chunks
+ * (lmrl_tq_history_chunk).  Tokenizers whose ids are the text's UTF-8 bytes only (the caller probes it); histories that fit without truncation.
+ * Every buffer is the caller's; all calls are asynchronous on `stream`.  One env per lane.  N envs, T = max_turns, G = max_new_tokens,
+ * Q = G + 1 question bytes, OG = oracle_max_new_tokens.
+ * ------------------------------------------------------------------------------------------ */
+#define LMRL_TQ_ORACLE_MAX_NEW 16
+typedef struct {
+    /* the episode record, one row per (env, turn) */
+    int32_t *gen;         /* [N][T][G] the guesser's generated ids */
+    int32_t *gen_len;     /* [N][T] */
+    uint8_t *q_text;      /* [N][T][Q] the question as the history holds it: decode(ids) under `removesuffix('\n') + '\n'` */
+    int32_t *q_len;       /* [N][T] */
+    int32_t *q_off;       /* [N][T] where the question's ids start in hist */
+    int32_t *ogen;        /* [N][T][OG] the oracle's generated ids */
+    int32_t *ogen_len;    /* [N][T] */
+    uint8_t *answer;      /* [N][T] 1 "Yes." / 0 "No." */
+    float *reward;        /* [N][T] -1, or 0 for the question that guessed the word */
+    uint8_t *done;        /* [N][T] */
+    uint8_t *flag;        /* [N][T] 1: affirmed, but not judged on the device (the host decides after the episode) */
+    int32_t *n_turns;     /* [N] questions asked */
+    uint8_t *live;        /* [N] */
+    float *ep_reward;     /* [N] */
+    int32_t *word;        /* [N] index of the hidden word */
+    /* the current turn */
+    int32_t *out_tok;     /* [N][G] the guesser's generation buffer (lmrl_gen_accept) */
+    int32_t *out_len;     /* [N] */
+    uint8_t *gen_active;  /* [N] */
+    int32_t *o_out_tok;   /* [N][OG] the oracle's generation buffer */
+    int32_t *o_out_len;   /* [N] */
+    uint8_t *o_active;    /* [N] */
+    int32_t *strip_b;     /* [N] str.strip() of the current question = bytes [strip_b, strip_e) of its q_text row */
+    int32_t *strip_e;     /* [N] */
+    uint8_t *ans;         /* [N] the current answer code */
+    int32_t *hist;        /* [N][hcap] canonical ids of the whole history: INITIAL_STR, question 1, answer 1, ... */
+    int32_t *hist_len;    /* [N] */
+    int32_t *feed_start;  /* [N] the guesser's pending feed = hist[feed_start, feed_start + feed_len) */
+    int32_t *feed_len;    /* [N] */
+    int32_t *o_prompt;    /* [N][pcap] the current oracle prompt */
+    int32_t *o_len;       /* [N] */
+    int32_t *o_prev;      /* [N][pcap] the previous turn's oracle prompt (its K/V rows are still in the oracle's cache) */
+    int32_t *o_prev_len;  /* [N] */
+    int32_t *o_keep;      /* [N] tokens of the current oracle prompt whose K/V rows are kept */
+    int32_t *flags;       /* [1] bit 0: an oracle prompt's new part outgrew its chunks; 1: history overflow; 2: oracle prompt overflow (pcap);
+                             3: a guesser feed outgrew its chunks */
+    int32_t hcap, pcap;
+} lmrl_tq_traj;
+
+/* host tables of lmrl_tq_create.  One string table (`bytes` / `str_off [n_strings + 1]`): the determiners, the function words and the generic
+ * nouns of the stand-in tagger (n_det, n_func, n_generic strings, in this order; envs/twenty_questions.py is their home), then every spelling's
+ * lower-cased token list as the active tagger produced it (`WordVariants.tokens`): spelling p = strings [spell_off[p], spell_off[p + 1]), word
+ * w = spellings [word_off[w], word_off[w + 1]).  prefix [n_words][prefix_cap] / prefix_len: the caller's encoding of
+ * "Answer the question about the object truthfully.\nobject: {word}\nquestion: "; suffix: of "\nanswer (yes or no): "; invalid_question: the
+ * bytes of INVALID_QUESTION; initial: the ids of INITIAL_STR; yes / no: of "Yes.\n" / "No.\n".  tok_blen [vocab]: 0 = the id adds nothing to a
+ * decoded text (lmrl_maze_tok_create).  eos tokens < 0: none. */
+typedef struct {
+    const uint8_t *bytes;
+    const int32_t *str_off, *spell_off, *word_off;
+    int32_t n_strings, n_spellings, n_words, n_det, n_func, n_generic;
+    const uint8_t *tok_blen;
+    int32_t vocab, eos_token, oracle_eos_token;
+    const int32_t *prefix, *prefix_len;
+    int32_t prefix_cap;
+    const int32_t *suffix;
+    int32_t suffix_len;
+    const uint8_t *invalid_question;
+    int32_t invalid_len;
+    const int32_t *initial;
+    int32_t initial_len;
+    const int32_t *yes;
+    int32_t yes_len;
+    const int32_t *no;
+    int32_t no_len;
+    int32_t max_new_tokens, oracle_max_new_tokens, max_turns;
+} lmrl_tq_tables;
+
+typedef struct lmrl_tq_ctx lmrl_tq_ctx;
+/* the context owns copies of the tables only.  host_only != 0: no device copies — only the lmrl_tq_host_* faces work (CPU tests). */
+lmrl_tq_ctx *lmrl_tq_create(const lmrl_tq_tables *tables, int host_only);
+void lmrl_tq_destroy(lmrl_tq_ctx *c);
+/* episode start.  Hidden word of env i: seeds_d[i] % n_words where deterministic_d[i] (NULL: nowhere), else draws_d[i] — the first
+ * _randbelow(n_words) of random.Random(seed), drawn by the caller with lmrl_mt_seed + lmrl_mt_randbelow.  Records and counters cleared, envs
+ * >= n_live idle, history = INITIAL_STR and pending as the guesser's first feed, both sessions' cache lengths 0. */
+int lmrl_tq_reset(lmrl_tq_ctx *c, const lmrl_tq_traj *tr, const uint64_t *seeds_d, const uint8_t *deterministic_d, const uint32_t *draws_d, int n_live,
+                  int32_t *guesser_len_d, int32_t *oracle_len_d, int n, void *stream);
+/* after the guesser's decode steps: generated ids -> the question text (UTF-8, errors="ignore"; `removesuffix('\n') + '\n'`) -> its canonical ids
+ * onto the history; Python str.strip() of it -> the oracle prompt prefix[word] ++ stripped question ++ suffix (finished envs: INVALID_QUESTION
+ * about their own word).  guesser_len_d: cut back to history + the generated ids that were forwarded AND are the canonical ids
+ * (keep_generated == 0: to the history alone); oracle_len_d: the longest common prefix of the previous and this prompt, at least one token
+ * forwarded — the rule of `GPT2PPOPolicy(reuse_kv=True)`. */
+int lmrl_tq_question(lmrl_tq_ctx *c, const lmrl_tq_traj *tr, int keep_generated, int32_t *guesser_len_d, int32_t *oracle_len_d, int n, void *stream);
+/* chunk j of n_chunks (chunk tokens per env) of the oracle prompts behind their kept prefixes: chunk_tok_d [N][chunk], chunk_cnt_d [N] */
+int lmrl_tq_oracle_prompt(lmrl_tq_ctx *c, const lmrl_tq_traj *tr, int j, int chunk, int n_chunks, int32_t *chunk_tok_d, int32_t *chunk_cnt_d, int n, void *stream);
+/* the same for the guesser's pending feed: the question's unforwarded canonical ids and the answer's (episode start: INITIAL_STR) */
+int lmrl_tq_history_chunk(lmrl_tq_ctx *c, const lmrl_tq_traj *tr, int j, int chunk, int n_chunks, int32_t *chunk_tok_d, int32_t *chunk_cnt_d, int n, void *stream);
+/* the oracle's generated ids -> strip().lower() -> yes|no at the start -> "Yes." / "No." (no match: "No."; a question equal to INVALID_QUESTION:
+ * "No." unread); scripted_d (int8 [N][script_turns], NULL: none; < 0: ask the model): the injected answer of turn min(t, script_turns - 1).  The
+ * answer's ids join the history and the guesser's feed. */
+int lmrl_tq_answer(lmrl_tq_ctx *c, const lmrl_tq_traj *tr, const int8_t *scripted_d, int script_turns, int n, void *stream);
+/* guessed (an affirmed question that names the word: `is_done` under rule_pos_tag, questions of code points < 0x80), reward, done (guessed, or
+ * max_conversation_length questions asked), the record, live flags.  An affirmed question with a byte >= 0x80 — with device_judge == 0 every
+ * affirmed question — is not guessed here: the game goes on and the turn is flagged. */
+int lmrl_tq_judge(lmrl_tq_ctx *c, const lmrl_tq_traj *tr, int device_judge, int max_conversation_length, int n, void *stream);
+/* the first n envs' episodes as single-trajectory PPO records (lmrl_ppo_records without chains): the whole history's ids, the questions' tokens as
+ * actions, each turn's reward on its question's last token, done [n]   (twenty_questions/ppo/train_ppo.py:322-352) */
+int lmrl_tq_ppo_records(lmrl_tq_ctx *c, const lmrl_tq_traj *tr, int n, int cap, int32_t *tokens_d, uint8_t *is_action_d, float *reward_d, int32_t *n_tok_d,
+                        uint8_t *done_d, void *stream);
+/* host faces of the text rules (the same functions on host memory; no GPU needed): the question (-> length; strip_range[2] = its strip()), the
+ * oracle prompt ids, the answer code, is_done (*judgeable = 0: a byte >= 0x80, not decided), the word draw */
+int lmrl_tq_host_question(const lmrl_tq_ctx *c, const int32_t *ids, int n, uint8_t *question_out, int cap, int32_t *strip_range);
+int lmrl_tq_host_oracle_prompt(const lmrl_tq_ctx *c, int word, const uint8_t *question, int n, int32_t *out, int cap);
+int lmrl_tq_host_answer(const lmrl_tq_ctx *c, const uint8_t *question, int qn, const int32_t *ids, int n);
+int lmrl_tq_host_is_done(const lmrl_tq_ctx *c, int word, const uint8_t *question, int n, int *judgeable);
+int lmrl_tq_host_draw_word(uint64_t seed, int deterministic, int n_words);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel-class timing with HIP events on the launch stream (used by bench.py for the live roofline figure).
  * mask bit t enables tag t; `work` accumulates the algorithmic flops (GEMM-class tags) or bytes (others) per launch.
  * ------------------------------------------------------------------------------------------ */

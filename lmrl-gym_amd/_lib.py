@@ -144,6 +144,20 @@ _SIGS = {
     "lmrl_chess_host_prompt_tokens": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_void_p, c_int]),
     "lmrl_chess_host_action_from_tokens": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "lmrl_chess_host_reply_word": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    "lmrl_tq_create": (c_void_p, [c_void_p, c_int]),
+    "lmrl_tq_destroy": (None, [c_void_p]),
+    "lmrl_tq_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_tq_question": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_tq_oracle_prompt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_tq_history_chunk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lmrl_tq_answer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lmrl_tq_judge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "lmrl_tq_ppo_records": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6),
+    "lmrl_tq_host_question": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "lmrl_tq_host_oracle_prompt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int]),
+    "lmrl_tq_host_answer": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    "lmrl_tq_host_is_done": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "lmrl_tq_host_draw_word": (c_int, [ctypes.c_uint64, c_int, c_int]),
     "lmrl_wordle_tok_create": (c_void_p, [c_void_p, c_void_p, c_int, c_int, c_int]),
     "lmrl_wordle_tok_destroy": (None, [c_void_p]),
     "lmrl_wordle_tok_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -287,6 +287,14 @@ def cmd_ppo(a):
         from lmrl_gym_amd.envs import maze as M
         env = M.setup_maze_env(a.maze_name, a.maze_describe_function, a.maze_reward_function, last_k=a.maze_last_k, max_steps=a.maze_max_steps)
         vocab = None
+    elif a.env == "twenty-questions":       # twenty_questions/ppo/train_ppo.py: a second resident model answers the questions inside the loop
+        from lmrl_gym_amd.envs import twenty_questions as TQ
+        ocfg, osd = _model(a.tq_oracle_model or a.model, max(len(tok), 50257))
+        tq_oracle = _engine(ocfg, osd)
+        words = TQ.get_default_word_list()[: a.tq_words]
+        env = TQ.BatchedTwentyQuestionsPolicyEnvironment(TQ.GPT2EngineOracle(tq_oracle, tok, max_input_length=a.tq_oracle_max_input_length, max_new_tokens=4,
+                                                                             eos_token_id=tok.encode("\n")[0]), words, a.tq_max_conversation_length, a.rollout_bsize)
+        vocab = None
     else:
         vocab, env = _wordle_env(a)
     step = 0
@@ -300,8 +308,17 @@ def cmd_ppo(a):
         from lmrl_gym_amd.chess_rollout import ChessRolloutEngine
         return ChessRolloutEngine(policy.engine, tok, env, a.rollout_bsize, max_new_tokens=min(a.max_output_length, 12), eos_token_id=tok.encode("\n")[0],
                                   max_input_length=a.max_input_length, opponent="device" if a.chess_random_opponent else env._vec.engine)
+
+    def tq_rollouts():
+        # both models, the env's text rules and the lock-step loop on the GPU (TwentyQuestionsRolloutEngine)
+        from lmrl_gym_amd.tq_rollout import TwentyQuestionsRolloutEngine
+        return TwentyQuestionsRolloutEngine(policy.engine, tq_oracle, tok, env, a.rollout_bsize, max_new_tokens=min(a.max_output_length, 12),
+                                            eos_token_id=tok.encode("\n")[0], max_input_length=a.max_input_length,
+                                            oracle_max_input_length=a.tq_oracle_max_input_length)
     if resident and a.env == "chess":
         ro_res = chess_rollouts()
+    elif resident and a.env == "twenty-questions":
+        ro_res = tq_rollouts()
     elif resident and a.env == "maze":
         from lmrl_gym_amd.maze_rollout import MazeRolloutEngine
         ro_res = MazeRolloutEngine(policy.engine, tok, env, a.rollout_bsize, max_new_tokens=min(a.max_output_length, 12), eos_token_id=tok.encode("\n")[0],
@@ -353,6 +370,11 @@ def cmd_ppo(a):
             ro = chess_rollouts()
             raw, summary = ro.text_env_eval(a.n_rollouts, seed_generator=iter(range(rnd * 10 ** 6, 10 ** 9)), temperature=a.policy_temperature or 1.0,
                                             top_k=int(a.policy_top_k or 0), sample_seed=rnd)
+            ro.close()
+        elif a.device_rollouts and a.env == "twenty-questions":
+            ro = tq_rollouts()
+            raw, summary = ro.text_env_eval(a.n_rollouts, seed_generator=iter(range(rnd * 10 ** 6, 10 ** 9)), temperature=a.policy_temperature or 1.0,
+                                            top_k=int(a.policy_top_k or 0), top_p=float(a.policy_top_p or 0.0), sample_seed=rnd)
             ro.close()
         elif a.device_rollouts:     # env + policy + lock-step loop on the GPU; same (interactions, summary) as text_env_eval
             ro = _device_rollouts(policy.engine, vocab, tok, a.rollout_bsize, a.bad_word_reward, min(a.max_output_length, 12))
@@ -567,7 +589,9 @@ def build_parser() -> argparse.ArgumentParser:
                                                "(the reference's Maze scripts evaluate in float32 by default)")
     sub.choices["ppo"].add_argument("--bc-data", default=None)
     pp = sub.choices["ppo"]
-    pp.add_argument("--env", default="wordle", choices=["wordle", "chess", "maze"])
+    pp.add_argument("--env", default="wordle", choices=["wordle", "chess", "maze", "twenty-questions"])
+    pp.add_argument("--tq-max-conversation-length", type=int, default=20); pp.add_argument("--tq-oracle-model", default=None, help="default: --model")
+    pp.add_argument("--tq-oracle-max-input-length", type=int, default=256); pp.add_argument("--tq-words", type=int, default=None, help="only the first N objects")
     pp.add_argument("--maze-name", default="double_t_maze"); pp.add_argument("--maze-describe-function", default="describe_observation_give_position")
     pp.add_argument("--maze-reward-function", default="standard_reward"); pp.add_argument("--maze-last-k", type=int, default=1)
     pp.add_argument("--maze-max-steps", type=int, default=100)

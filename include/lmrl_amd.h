@@ -1360,6 +1360,31 @@ int lmrl_kv_reorder_f32(const float *src_kv_d, const int32_t *src_len_d, const f
                         const int32_t *from_d, float *dst_kv_d, int32_t *dst_len_d, float *dst_hidden_d, float *dst_last_x_d, int b, int tmax, int n_layer,
                         int d, const int32_t *go_d, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GPT-J on the fp32 rollout mode (csrc/attn_rope_f32.hip; `lmrl_gym_amd.gptj_f32_engine.GPTJEngineF32` sequences these with lmrl_sgemm,
+ * lmrl_layernorm_*, lmrl_gelu_fwd and the lmrl_chunk_*_f32 calls above).
+ *   lmrl_rope_gptj_f32   GPT-J's rotary embedding ("rotate every two"), in place on q and k of qkv_d fp32 [rows][3 * n_head * head_dim]: for pair
+ *                        i < rotary_dim / 2 of every head,  y[2i] = x[2i] cos - x[2i+1] sin,  y[2i+1] = x[2i+1] cos + x[2i] sin  with
+ *                        sin = sincos_d[pos][i], cos = sincos_d[pos][rotary_dim / 2 + i]; sincos_d fp32 [n_pos][rotary_dim] = [sin | cos] is built by
+ *                        the host (HF `create_sinusoidal_positions`).  v, dims >= rotary_dim and rows with pos_d[row] < 0 are not touched.
+ *                        rotary_dim even, <= head_dim.  The positions are read back and checked first (one stream synchronisation): a row with
+ *                        pos >= n_pos is LMRL_ERR_ARG and nothing is launched.  Not usable inside a stream capture (LMRL_ERR_ARG).
+ *   lmrl_rope_gptj_f32_async  the same launch without the read-back (no synchronisation: capturable).  The kernel itself never reads the table
+ *                        for a row with pos >= n_pos — such a row passes through unrotated — so the caller has to bound the positions
+ *                        (GPTJEngineF32 does, on the host, from its cache-length bound).
+ *   lmrl_attn_cached_hd_f32  lmrl_attn_cached_f32 with the head dim passed in, head_dim in {64, 128, 256} (else LMRL_ERR_ARG): same cache layout
+ *                        ([b][tmax][n_head * head_dim]) and arguments, scores scaled by 1 / sqrt(head_dim), one launch for any c (chunk and
+ *                        decode).  One wave per (env, head, query); keys walked in tiles of lmrl_attn_hd_key_tile() positions; online softmax and
+ *                        accumulation in fp32.  An env whose new rows do not fit (len + j >= tmax) is skipped.
+ * ------------------------------------------------------------------------------------------ */
+int lmrl_rope_gptj_f32(float *qkv_d, const int32_t *pos_d, const float *sincos_d, int rows, int n_head, int head_dim, int rotary_dim, int n_pos,
+                       void *stream);
+int lmrl_rope_gptj_f32_async(float *qkv_d, const int32_t *pos_d, const float *sincos_d, int rows, int n_head, int head_dim, int rotary_dim, int n_pos,
+                             void *stream);
+int lmrl_attn_cached_hd_f32(const float *qkv_d, float *kcache_d, float *vcache_d, const int32_t *len_d, const int32_t *cnt_d, float *out_d, int b, int c,
+                            int n_head, int head_dim, int tmax, void *stream);
+int lmrl_attn_hd_key_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,10 @@ _SIGS = {
     "lmrl_beam_select": (c_int, [c_void_p] * 8 + [c_int] * 10 + [c_float, c_float, c_void_p]),
     "lmrl_gpt2_kv_reorder": (c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p]),
     "lmrl_kv_reorder_f32": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "lmrl_rope_gptj_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lmrl_rope_gptj_f32_async": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lmrl_attn_cached_hd_f32": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lmrl_attn_hd_key_tile": (c_int, []),
 }
 
 

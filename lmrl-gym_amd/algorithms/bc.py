@@ -118,6 +118,8 @@ class GPT2BCTrain:
 
     def __init__(self, model: GPT2F32, pad_token_id: int, non_action_weight: float = 0.0, lr: float = 1e-4, weight_decay: float = 0.0,
                  grad_accum_steps: int = 1):
+        from ..gptj_f32_engine import refuse_gptj
+        refuse_gptj("GPT2BCTrain", model)
         self.model, self.pad, self.w = model, pad_token_id, non_action_weight
         self.opt = AdamW(model.p, lr, weight_decay=weight_decay, every_k=grad_accum_steps)
         self.last_grads = None

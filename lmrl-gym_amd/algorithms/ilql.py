@@ -171,6 +171,8 @@ class GPT2ILQLTrain:
         the `should_take_action` rows: the L2 terms of `ilql_loss` select by should_take_action alone, n and the CQL terms by
         should_take_action x attention_mask (ilql/base_interface.py:22-119), so that row set covers every Q term — instead of on all B*T
         rows; same loss, logs and gradients (rows outside the set contribute exact zeros), fewer flops in proportion to the mask density."""
+        from ..gptj_f32_engine import refuse_gptj
+        refuse_gptj("GPT2ILQLTrain", base, target_base)
         import torch
         self.compact_q_rows = compact_q_rows
         self.base, self.q1, self.q2, self.v = base, q1_head, q2_head, v_head

@@ -130,6 +130,8 @@ class GPT2MCTrain:
 
     def __init__(self, base, q_head, pad_token_id: int, loss_kwargs, lr: float = 3e-5, weight_decay: float = 0.0,
                  grad_accum_steps: int = 1, detach_q: bool = False):
+        from ..gptj_f32_engine import refuse_gptj
+        refuse_gptj("GPT2MCTrain", base)
         from ..train.gpt2_f32 import AdamW
         self.base, self.q_head, self.pad, self.loss_kwargs, self.detach_q = base, q_head, pad_token_id, dict(loss_kwargs), detach_q
         self.base_opt = AdamW(base.p, lr, weight_decay=weight_decay, every_k=grad_accum_steps)

@@ -248,6 +248,8 @@ class GPT2PPOTrain:
     def __init__(self, policy: GPT2F32, value_head: LinearHeadF32, pad_token_id: int, loss_kwargs: Dict[str, float],
                  lr: float = 1e-5, weight_decay: float = 0.0, grad_accum_steps: int = 1, bc_loss_weight: float = 0.0,
                  bc_non_action_weight: float = 0.0):
+        from ..gptj_f32_engine import refuse_gptj
+        refuse_gptj("GPT2PPOTrain", policy)
         self.policy, self.value_head, self.pad = policy, value_head, pad_token_id
         self.loss_kwargs = dict(loss_kwargs)
         self.policy_opt = AdamW(policy.p, lr, weight_decay=weight_decay, every_k=grad_accum_steps)

@@ -15,6 +15,9 @@ stand-ins), `load_msgpack_tree` reads it back leaf for leaf and `save_msgpack_tr
 Parameter naming: HF-Flax GPT-2 (`transformer/{wte,wpe}/embedding`, `transformer/h/<l>/{ln_1,ln_2}/{scale,bias}`,
 `.../attn/{c_attn,c_proj}/{kernel,bias}`, `.../mlp/{c_fc,c_proj}/{kernel,bias}`, `transformer/ln_f/{scale,bias}`) with
 `FlaxConv1D` kernels stored `[out, in]` — the transpose of the PyTorch `Conv1D` `[in, out]` layout our state dicts use.
+GPT-J (`load_gptj_checkpoint`, `load_hf_pytorch_gptj`): HF-Flax GPT-J names (`transformer/wte/embedding`, `transformer/h/<l>/ln_1/{scale,bias}`,
+`.../attn/{q,k,v,out}_proj/kernel`, `.../mlp/{fc_in,fc_out}/{kernel,bias}`, `transformer/ln_f/{scale,bias}`, `lm_head/{kernel,bias}`) with `nn.Dense`
+kernels `[in, out]` — the transpose of the PyTorch `nn.Linear` `[out, in]` weights the GPT-J state dicts use.  Restated, like the GPT-2 map.
 Heads: `LinearHead` = `{"dense": {"kernel", "bias"}}`, `MLPHead` = `{"dense1": {...}, "dense2": {...}}`
 (`LLM_RL/heads/linear_head.py:112-123`, `mlp_head.py:139-148`).
 """
@@ -276,3 +279,97 @@ def load_hf_pytorch_gpt2(path: str):
     cfg = GPT2Config(n_layer=cj["n_layer"], n_head=cj["n_head"], d_model=d, d_ff=cj.get("n_inner") or 4 * d, vocab=sd["wte.weight"].shape[0],
                      n_pos=sd["wpe.weight"].shape[0], ln_eps=cj.get("layer_norm_epsilon", 1e-5), **_pdrop_fields(cj))
     return cfg, sd
+
+
+# ---------------------------------------------------------------------------------------------- GPT-J name maps
+_GPTJ_DENSE = (("attn", "q_proj", False), ("attn", "k_proj", False), ("attn", "v_proj", False), ("attn", "out_proj", False),
+               ("mlp", "fc_in", True), ("mlp", "fc_out", True))
+
+
+def flax_gptj_params_to_state_dict(params: Dict[str, Any]) -> Dict[str, np.ndarray]:
+    """HF-Flax GPT-J param tree -> HF PyTorch GPT-J names (`nn.Linear` weights [out, in]) as float32 numpy arrays."""
+    tr = params["transformer"]
+    f = lambda a: np.asarray(a, dtype=np.float32)
+    sd = {"transformer.wte.weight": f(tr["wte"]["embedding"]), "transformer.ln_f.weight": f(tr["ln_f"]["scale"]),
+          "transformer.ln_f.bias": f(tr["ln_f"]["bias"]), "lm_head.weight": np.ascontiguousarray(f(params["lm_head"]["kernel"]).T),
+          "lm_head.bias": f(params["lm_head"]["bias"])}
+    for l in sorted(tr["h"], key=int):
+        blk, p = tr["h"][l], f"transformer.h.{int(l)}."
+        sd[p + "ln_1.weight"], sd[p + "ln_1.bias"] = f(blk["ln_1"]["scale"]), f(blk["ln_1"]["bias"])
+        for mod, name, has_bias in _GPTJ_DENSE:
+            sd[p + f"{mod}.{name}.weight"] = np.ascontiguousarray(f(blk[mod][name]["kernel"]).T)      # [in,out] -> [out,in]
+            if has_bias:
+                sd[p + f"{mod}.{name}.bias"] = f(blk[mod][name]["bias"])
+    return sd
+
+
+def state_dict_to_flax_gptj_params(sd: Dict[str, Any]) -> Dict[str, Any]:
+    sd = {(k if k.startswith(("transformer.", "lm_head.")) else "transformer." + k): _np(v).astype(np.float32) for k, v in sd.items()}
+    n_layer = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("transformer.h."))
+    tr: Dict[str, Any] = {"wte": {"embedding": sd["transformer.wte.weight"]},
+                          "ln_f": {"scale": sd["transformer.ln_f.weight"], "bias": sd["transformer.ln_f.bias"]}, "h": {}}
+    for l in range(n_layer):
+        p = f"transformer.h.{l}."
+        blk: Dict[str, Any] = {"ln_1": {"scale": sd[p + "ln_1.weight"], "bias": sd[p + "ln_1.bias"]}, "attn": {}, "mlp": {}}
+        for mod, name, has_bias in _GPTJ_DENSE:
+            blk[mod][name] = {"kernel": np.ascontiguousarray(sd[p + f"{mod}.{name}.weight"].T)}
+            if has_bias:
+                blk[mod][name]["bias"] = sd[p + f"{mod}.{name}.bias"]
+        tr["h"][str(l)] = blk
+    return {"transformer": tr, "lm_head": {"kernel": np.ascontiguousarray(sd["lm_head.weight"].T), "bias": sd["lm_head.bias"]}}
+
+
+def _gptj_config(cj: Dict[str, Any], sd: Dict[str, np.ndarray], where: str):
+    from .gptj_f32_engine import GPTJConfig
+    if "n_head" not in cj:
+        # not recoverable from the tensors (q_proj is [d, d] for any head count): refuse instead of guessing
+        raise ValueError(f"{where}/config.json has no 'n_head': cannot reconstruct the GPT-J configuration")
+    if "rotary_dim" not in cj:
+        raise ValueError(f"{where}/config.json has no 'rotary_dim': cannot reconstruct the GPT-J configuration")
+    shapes = dict(n_layer=1 + max(int(k.split(".")[2]) for k in sd if k.startswith("transformer.h.")), n_embd=sd["transformer.wte.weight"].shape[1],
+                  n_inner=sd["transformer.h.0.mlp.fc_in.weight"].shape[0], vocab_size=sd["transformer.wte.weight"].shape[0])
+    return GPTJConfig.from_hf({**cj, **shapes, "model_type": "gptj"})
+
+
+def checkpoint_model_family(path: str) -> str:
+    """"gptj" or "gpt2", from `model_type` of `<path>/config.json` (missing file or field: "gpt2", the layout this module has always read)."""
+    cj = os.path.join(path, "config.json")
+    if os.path.exists(cj):
+        with open(cj) as f:
+            return "gptj" if json.load(f).get("model_type") == "gptj" else "gpt2"
+    return "gpt2"
+
+
+def load_gptj_checkpoint(path: str):
+    """-> (GPTJConfig, HF-PyTorch-named state dict of float32 numpy arrays) from `<path>/{config.json, params.msgpack|train_state.msgpack}`."""
+    cfg_json, tree = _load_params_dir(path)
+    sd = flax_gptj_params_to_state_dict(tree)
+    return _gptj_config(cfg_json, sd, path), sd
+
+
+def save_gptj_checkpoint(path: str, cfg, state_dict: Dict[str, Any], extra_config: Optional[Dict[str, Any]] = None) -> None:
+    os.makedirs(path, exist_ok=True)
+    cj = cfg.to_hf()
+    cj.update(extra_config or {})
+    with open(os.path.join(path, "config.json"), "w") as f:
+        json.dump(cj, f, indent=2)
+    save_msgpack_tree(os.path.join(path, "params.msgpack"), state_dict_to_flax_gptj_params(state_dict))
+
+
+def load_hf_pytorch_gptj(path: str):
+    """HF PyTorch GPT-J directory (`config.json` + `model.safetensors` | `pytorch_model.bin`) -> (GPTJConfig, state dict)."""
+    with open(os.path.join(path, "config.json")) as f:
+        cj = json.load(f)
+    st = os.path.join(path, "model.safetensors")
+    if os.path.exists(st):
+        from safetensors.numpy import load_file
+        raw = load_file(st)
+    else:
+        import torch
+        raw = {k: v.float().numpy() for k, v in torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu").items()}
+    sd = {}
+    for k, v in raw.items():
+        if k.endswith((".attn.bias", ".attn.masked_bias", ".attn.embed_positions")):      # causal-mask / rotary buffers of older HF versions
+            continue
+        sd[k if k.startswith(("transformer.", "lm_head.")) else "transformer." + k] = np.asarray(v, dtype=np.float32)
+    return _gptj_config(cj, sd, path), sd

@@ -106,6 +106,8 @@ class ChessRolloutEngine:
     def __init__(self, engine, tokenizer, env, batch: int, max_new_tokens: int = 8, eos_token_id: Optional[int] = None, max_input_length: int = 256,
                  max_turns: Optional[int] = None, opponent="device", prompt_bound: Optional[int] = None, reuse_kv: bool = True,
                  session_flags: int = FWD_RAGGED_ALWAYS):
+        from .gptj_f32_engine import refuse_gptj
+        refuse_gptj("ChessRolloutEngine", engine)
         import torch
         t = torch
         venv = getattr(env, "_vec", env)

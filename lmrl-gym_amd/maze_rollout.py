@@ -99,6 +99,8 @@ class MazeRolloutEngine:
                  prefix_indexed: bool = True,
                  max_turns: Optional[int] = None, value_engine: Optional[GPT2Engine] = None, q1_head: Optional[dict] = None,
                  q2_head: Optional[dict] = None, beta: float = 0.0, session_flags: int = FWD_RAGGED_ALWAYS):
+        from .gptj_f32_engine import refuse_gptj
+        refuse_gptj("MazeRolloutEngine", engine, value_engine)
         import torch
         t = torch
         if value_engine is not None:

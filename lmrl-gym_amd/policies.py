@@ -88,6 +88,9 @@ class GPT2PPOPolicy(BatchedTextPolicy):
             raise ValueError(f"num_beams = {num_beams}")
         if num_beams > 1 and do_sample:
             raise NotImplementedError("Beam sampling is currently not implemented.")
+        if num_beams > 1:
+            from .gptj_f32_engine import refuse_gptj
+            refuse_gptj("Beam search (num_beams > 1)", engine)
         self.num_beams, self.length_penalty, self.early_stopping = int(num_beams), float(length_penalty), bool(early_stopping)
         self._beam = None
         self.engine, self.tokenizer = engine, tokenizer
@@ -228,6 +231,8 @@ class GPT2ValuePolicy(GPT2PPOPolicy):
     MC-returns policy (pi_beta + beta * Q).  pi_beta and the value base are engines of one class (and one matmul mode)."""
 
     def __init__(self, pi_beta: GPT2Engine, value_base: GPT2Engine, q1_head: dict, q2_head: Optional[dict], beta: float, tokenizer, **kw):
+        from .gptj_f32_engine import refuse_gptj
+        refuse_gptj("GPT2ValuePolicy (the ILQL / MC value policies)", pi_beta, value_base)
         super().__init__(pi_beta, tokenizer, **kw)
         check_value_policy(pi_beta, value_base, (q1_head, q2_head))
         self.value_base, self.q1, self.q2, self.beta = value_base, q1_head, q2_head, beta
@@ -260,6 +265,23 @@ class GPT2ValuePolicy(GPT2PPOPolicy):
             ops.append((gen.qh[i], head.get("w2_x3", head["w2"]), head["b2"]))
         params.beta = self.beta
         return pi_ses.sample(params, active=active_d, logits_out=logits_out, q1=ops[0], q2=ops[1], want_logprob=False)
+
+
+class GPTJPPOPolicy(GPT2PPOPolicy):
+    """`GPTJPPOPolicy` of LLM_RL/algorithms/ppo/gptj/interface.py (also the BC policy of the GPT-J task scripts): `GPT2PPOPolicy` on a
+    `gptj_f32_engine.GPTJEngineF32` — same prompt handling, KV reuse, samplers and stopping rules; sampling or greedy (no beam search)."""
+
+    def __init__(self, engine, tokenizer, **kw):
+        from .gptj_f32_engine import is_gptj
+        if not is_gptj(engine):
+            raise TypeError(f"GPTJPPOPolicy takes a GPTJEngineF32, not a {type(engine).__name__} (GPT-2 engines: GPT2PPOPolicy)")
+        super().__init__(engine, tokenizer, **kw)
+
+    def set_params(self, engine) -> None:
+        from .gptj_f32_engine import is_gptj
+        if not is_gptj(engine):
+            raise TypeError(f"GPTJPPOPolicy takes a GPTJEngineF32, not a {type(engine).__name__}")
+        super().set_params(engine)
 
 
 def check_value_policy(pi_beta, value_base, heads) -> None:

@@ -158,6 +158,8 @@ class WordleRolloutEngine:
         (`GPT2ValueRLGeneration`, value_rl_base/gpt2/generation.py:97-119): `engine` is pi_beta, `value_engine` the value base
         whose last hidden state feeds the Q heads (`policies.heads_to_engine_layout(..., engine=engine)` dicts); logits = pi_beta + beta * min(Q1, Q2)
         (+ beta * Q1 without a q2_head: the MC-returns policy).  Both transformers are `GPT2Engine`s or both `GPT2EngineF32`s of one matmul mode."""
+        from .gptj_f32_engine import refuse_gptj
+        refuse_gptj("WordleRolloutEngine", engine, value_engine)
         import torch
         t = torch
         if value_engine is not None:

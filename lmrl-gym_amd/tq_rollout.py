@@ -141,6 +141,8 @@ class TwentyQuestionsRolloutEngine:
     def __init__(self, engine, oracle_engine, tokenizer, env, batch: int, max_new_tokens: int, eos_token_id: Optional[int], max_input_length: int,
                  oracle_max_input_length: int, oracle_max_new_tokens: int = 4, judge: str = "auto", out_str_process: Optional[Callable[[str], str]] = None,
                  reuse_generated: bool = True):
+        from .gptj_f32_engine import refuse_gptj
+        refuse_gptj("TwentyQuestionsRolloutEngine", engine, oracle_engine)
         import torch
         t = torch
         if not hasattr(env, "word_list") or not hasattr(env, "max_conversation_length"):

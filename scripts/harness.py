@@ -8,6 +8,7 @@
     python scripts/harness.py filtered-bc --device-rollouts 1 --device-data 1        # wordle/online_filtered_bc, every round resident in HBM
     python scripts/harness.py bc-eval                                                # llm_rl_scripts/wordle/bc/eval_bc_gpt2.py
     python scripts/harness.py maze-eval                                              # llm_rl_scripts/maze/bc/fully_observed_bc.py (eval part)
+    python scripts/harness.py bc-eval  --model-family gptj --model random:gptj-tiny  # llm_rl_scripts/wordle/bc/eval_bc.py (GPT-J, fp32 engine)
     python scripts/harness.py gen-data --n-data 1000 --out d.jsonl                   # llm_rl_scripts/wordle/misc/data_gen.py
     python scripts/harness.py gen-data --policy optimal --start-word raise --device-loop 1 --out d.jsonl   # scripted policies + loop on the device
     python scripts/harness.py optimal-perf --n 1000                                  # llm_rl_scripts/wordle/misc/optimal_perf.py
@@ -15,7 +16,8 @@
 Hyper-parameter names and defaults are the reference scripts' own.  Not carried over: tyro, wandb, GCS, mesh-shape flags (one
 process per GPU + `torch.distributed.run` instead).  `--model` is a checkpoint directory in the reference layout
 (`lmrl_gym_amd.checkpoints`) or `random:<tiny|small|medium>`; the GPT-2 tokenizer is `transformers.AutoTokenizer('gpt2')` when its
-files are available, else the Wordle-alphabet adapter (`datasets.WordleTokenizer`).
+files are available, else the Wordle-alphabet adapter (`datasets.WordleTokenizer`).  `--model-family gptj` (bc-eval and maze-eval): `--model` is a GPT-J
+checkpoint directory (HF PyTorch, or the reference's flax layout) or `random:gptj-tiny`; every other subcommand and `--device-rollouts 1` refuse it.
 """
 from __future__ import annotations
 
@@ -82,9 +84,30 @@ def _tokenizer(wordle: bool = True):
         return WordleTokenizer() if wordle else ByteTokenizer()
 
 
-def _model(spec: str, vocab: int):
+def _model_gptj(spec: str, vocab: int):
+    """--model-family gptj: `random:gptj-tiny` or a GPT-J checkpoint directory (HF PyTorch layout, or the reference's flax layout)."""
+    from lmrl_gym_amd import checkpoints as C
+    from lmrl_gym_amd.gptj_f32_engine import GPTJConfig, init_hf_style_gptj_state_dict
+    if spec.startswith("random:"):
+        sizes = {"gptj-tiny": GPTJConfig(2, 2, 128, 32, 256, vocab, 2048)}
+        if spec.split(":")[1] not in sizes:
+            raise SystemExit(f"--model-family gptj: --model {spec} is not one of " + ", ".join("random:" + k for k in sizes))
+        cfg = sizes[spec.split(":")[1]]
+        return cfg, init_hf_style_gptj_state_dict(cfg, seed=0)
+    import torch
+    loader = C.load_hf_pytorch_gptj if os.path.exists(os.path.join(spec, "model.safetensors")) or os.path.exists(os.path.join(spec, "pytorch_model.bin")) \
+        else C.load_gptj_checkpoint
+    cfg, sd = loader(spec)
+    return cfg, {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+
+
+def _model(spec: str, vocab: int, family: str = "gpt2"):
     from lmrl_gym_amd import checkpoints as C
     from lmrl_gym_amd.gpt2 import GPT2Config, init_hf_style_state_dict
+    if family == "gptj":
+        return _model_gptj(spec, vocab)
+    if spec.startswith("random:gptj"):
+        raise SystemExit(f"--model {spec} needs --model-family gptj")
     if spec.startswith("random:"):
         cfg = dict(tiny=GPT2Config(2, 2, 128, 256, vocab, 128), small=GPT2Config.gpt2_small(vocab), medium=GPT2Config.gpt2_medium(vocab))[spec.split(":")[1]]
         return cfg, init_hf_style_state_dict(cfg, seed=0)
@@ -100,6 +123,9 @@ def _engine(cfg, params, kind: str = "bf16"):
     from lmrl_gym_amd import _lib
     from lmrl_gym_amd.gpt2 import GPT2Engine
     sd = {k: (v.detach().cpu() if hasattr(v, "detach") else v) for k, v in params.items()}
+    if getattr(cfg, "model_family", "gpt2") == "gptj":      # GPT-J runs on the fp32 engine only (its one matmul mode), whatever `kind` says
+        from lmrl_gym_amd.gptj_f32_engine import GPTJEngineF32
+        return GPTJEngineF32(cfg, sd, _lib.require_gpu())
     if kind == "bf16":
         return GPT2Engine(cfg, sd, _lib.require_gpu())
     from lmrl_gym_amd.gpt2_f32_engine import GPT2EngineF32
@@ -513,7 +539,7 @@ def cmd_bc_eval(a):
     from lmrl_gym_amd import environment as E
     from lmrl_gym_amd.policies import GPT2PPOPolicy
     tok = _tokenizer()
-    cfg, sd = _model(a.model, max(len(tok), 50257))
+    cfg, sd = _model(a.model, max(len(tok), 50257), a.model_family)
     policy = GPT2PPOPolicy(_engine(cfg, sd), tok, max_input_length=a.policy_max_input_length, max_new_tokens=a.policy_max_output_length,
                            do_sample=a.policy_do_sample, temperature=a.policy_temperature, top_k=None if a.policy_top_k is None else int(a.policy_top_k),
                            top_p=a.policy_top_p, num_beams=a.policy_num_beams, eos_token_id=tok.encode("\n")[0], out_str_process=lambda x: x.removesuffix("\n") + "\n")
@@ -533,7 +559,7 @@ def cmd_maze_eval(a):
     from lmrl_gym_amd.envs import maze as M
     from lmrl_gym_amd.policies import GPT2PPOPolicy
     tok = _tokenizer(wordle=False)
-    cfg, sd = _model(a.model, max(len(tok), 50257))
+    cfg, sd = _model(a.model, max(len(tok), 50257), a.model_family)
     policy = GPT2PPOPolicy(_engine(cfg, sd, a.policy_engine), tok, max_input_length=a.max_input_length, max_new_tokens=a.max_output_length, do_sample=False,
                            eos_token_id=tok.encode("\n")[0], out_str_process=lambda x: x.removesuffix("\n") + "\n")
     env = M.setup_maze_env(a.maze_name, a.describe_function, a.reward_function, last_k=a.last_k, max_steps=a.max_steps)
@@ -556,6 +582,9 @@ def build_parser() -> argparse.ArgumentParser:
         p = sub.add_parser(name)
         p.set_defaults(fn=fn)
         p.add_argument("--model", default="random:tiny", help="checkpoint directory (reference layout or HF PyTorch) or random:<tiny|small>")
+        p.add_argument("--model-family", default="gpt2", choices=["gpt2", "gptj"],
+                       help="gptj (bc-eval and maze-eval only, without --device-rollouts): --model is random:gptj-tiny or a GPT-J checkpoint directory; "
+                            "the policy runs on GPTJEngineF32 (fp32)")
         p.add_argument("--vocab-file", default="wordle_official_400.txt")
         p.add_argument("--out", default=None)
         p.add_argument("--device-rollouts", type=int, default=0, help="1 = run the rollouts (bc-eval, ilql evaluation, ppo data collection: Wordle, Maze, chess) on the device-resident engine")
@@ -622,6 +651,15 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    if getattr(a, "model_family", "gpt2") == "gptj":
+        # GPT-J is inference on the fp32 engine through the text policies: no train step, no device-resident rollout loop
+        if a.cmd not in ("bc-eval", "maze-eval"):
+            raise SystemExit(f"--model-family gptj is not available for `{a.cmd}`: GPT-J training is not implemented (bc-eval and maze-eval take it)")
+        if getattr(a, "device_rollouts", 0):
+            raise SystemExit("--model-family gptj is not available with --device-rollouts 1 (the device-resident rollout loops run GPT-2 engines only); "
+                             "use --device-rollouts 0")
+        if getattr(a, "policy_num_beams", 1) > 1:
+            raise SystemExit("--model-family gptj is not available with --policy-num-beams > 1 (beam search runs on GPT-2 engines only)")
     if getattr(a, "policy_num_beams", 1) > 1 and getattr(a, "device_rollouts", 0):
         # the device-resident rollout engines sample (temperature / top_k / top_p); beam search runs in the text policies' act() only
         raise SystemExit("--policy-num-beams > 1 is not available with --device-rollouts 1 (the device rollout loops do not run beam search); "

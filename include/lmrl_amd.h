@@ -390,6 +390,23 @@ void lmrl_gpt2_destroy(lmrl_gpt2 *m);
  * rollout engine after every round: train_ppo_gpt2.py `policy.set_params(...)`): re-derive the model-owned LayerNorm-folded copies on `stream`.
  * Pointers held by sessions and captured hipGraphs stay valid. */
 int lmrl_gpt2_refresh(lmrl_gpt2 *m, void *stream);
+/*
+ * Pinned prefix: the K/V rows (and last hidden state) of a fixed token prefix, held in the cache of a 1-env KV session, as a derived product of
+ * the weights — like the LayerNorm-folded copies.  `pin` prefills the prefix once on `stream`: *len_d := 0, then one forward of 1 env x 8 slots
+ * per 8 tokens through the code path of lmrl_gpt2_forward with `flags` (the session's LMRL_FWD_* bits), i.e. launch for launch what the
+ * session's own reset + chunk forwards would do; the rows are bit-identical to theirs.  The model handle remembers the pin, and
+ * lmrl_gpt2_refresh re-runs that prefill for every pin, after the fold kernels, on the stream it is given.  Every writer of the weights
+ * already has to call lmrl_gpt2_refresh, so a pinned prefix cannot go stale without the folded weights going stale too; consumers
+ * (lmrl_gpt2_kv_broadcast out of the pinned cache, also inside captured hipGraphs) need no prefill of their own.
+ * All buffers are the caller's and must stay alive and unchanged in address until lmrl_gpt2_unpin_prefix(kv_d) or lmrl_gpt2_destroy (which
+ * drops the list); there is no process-wide state.  kv_d: cache of lmrl_gpt2_kv_bytes(m, 1, tmax); ws_d: lmrl_gpt2_ws_bytes(m, 1, 8), used
+ * by pin and by every refresh (its per-env index slot holds the chunk's token count); tokens_d: device int32, READABLE up to the next multiple
+ * of 8 entries (the slots past n_tokens are not used); 1 <= n_tokens <= tmax; last_hidden_d optional (bf16 [d]).  A cache can be pinned once
+ * (LMRL_ERR_ARG with an lmrl_last_error() text otherwise); unpinning a cache that is not pinned is LMRL_ERR_ARG.
+ */
+int lmrl_gpt2_pin_prefix(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, const int32_t *tokens_d, int n_tokens, int32_t *len_d,
+                         void *last_hidden_d, unsigned flags, void *stream);
+int lmrl_gpt2_unpin_prefix(lmrl_gpt2 *m, const void *kv_d);
 size_t lmrl_gpt2_kv_bytes(const lmrl_gpt2 *m, int b, int tmax);
 size_t lmrl_gpt2_ws_bytes(const lmrl_gpt2 *m, int b, int c);
 /*
@@ -412,13 +429,20 @@ size_t lmrl_gpt2_ws_bytes(const lmrl_gpt2 *m, int b, int c);
                                           * K split over the waves of a workgroup, every load issued up front) — 7-16 us -> ~3 us per product at 8 rows; same formulas, K summed in
                                           * 8 slices (not bit-identical to the tile kernels: a per-session choice) */
 #define LMRL_FWD_FULL_LAST_LAYER 32u /* chunk forwards: run the last layer's projection + MLP on every row (default: only on each env's last new token — the only row whose hidden state is returned; A/B and cross-check, bit-identical) */
-/* bits 16-31: reserved — the product library rejects them (LMRL_ERR_ARG). */
+/* bits 16-29: reserved — the product library rejects them (LMRL_ERR_ARG). */
+#define LMRL_FWD_PRE_EMBEDDED (1u << 31) /* per CALL (c = 1, LN-folded path; not ragged, skinny or prefixed — LMRL_ERR_ARG otherwise): the row embeddings (fp32 and bf16)
+                                          * and moment slot 0 of every row are already in ws_d for these tokens_d / cnt_d / len_d (lmrl_wordle_sample_accept_embed wrote
+                                          * them): the forward skips its embedding launch.  Bits 0-7 are taken and bits 8-15 carry the shared-prefix length, so the
+                                          * switch sits beside LMRL_FWD_SKINNY above the reserved range */
 /* bits 8-15: LMRL_FWD_SHARED_PREFIX(n) — positions [0, n) of EVERY env's cache hold the same K/V rows as env 0's (the caller copied them
  * with lmrl_gpt2_kv_broadcast and has not reset the cache since): the decode attention then reads them from env 0 (one L2-resident copy)
  * instead of once per env.  Results are bit-identical; a wrong promise reads env 0's prefix for every env. */
 #define LMRL_FWD_SHARED_PREFIX(n) (((unsigned)(n) & 0xffu) << 8)
 int lmrl_gpt2_forward(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, const int32_t *tokens_d, const int32_t *cnt_d,
                       int32_t *len_d, int b, int c, void *last_hidden_d, void *all_hidden_d, unsigned flags, void *stream);
+/* 1 if a single-token forward of b envs with these session flags (no all_hidden_d, no attached prefix) accepts LMRL_FWD_PRE_EMBEDDED, else 0:
+ * the library's own path choice (LN-folded, not ragged, not skinny), for callers that pick between the fused and the three-launch tail. */
+int lmrl_gpt2_forward_takes_pre_embedded(const lmrl_gpt2 *m, int b, unsigned flags);
 
 /*
  * Shared prompt prefix: copy positions [0, n_pos) of the single env of a 1-env KV session (src) into all `b` envs of dst,
@@ -562,6 +586,11 @@ typedef struct {
                              * path would not (same tokens either way) */
 } lmrl_sample_params;
 #define LMRL_SAMPLE_WANT_LOGITS 1
+#define LMRL_SAMPLE_KEEP_PARTIALS 2 /* lmrl_lm_head_sample: leave the per-(row, tile) partials in ws_d and do NOT launch the reduce — the caller merges them
+                                     * (lmrl_wordle_sample_accept_embed); token_d / logprob_d are not written, but logprob_d (null or not) still selects whether
+                                     * the partials carry the log-sum-exp pieces: pass the SAME logprob_d, null or not, to both calls — a log-prob merged from
+                                     * partials made with logprob_d = NULL is garbage.  Policy-only Philox or greedy sampling without
+                                     * top_k / top_p only (LMRL_ERR_ARG otherwise: no other path leaves those partials) */
 #define LMRL_RNG_PHILOX 0
 #define LMRL_RNG_JAX 1
 /* host faces of the LMRL_RNG_JAX stream: the Threefry-2x32 (20 rounds) block function and words [i0, i0 + count) of
@@ -696,6 +725,15 @@ int lmrl_wordle_tok_begin(lmrl_wordle_tok_ctx *c, const lmrl_wordle_traj *tr, in
  * next_tok_d/next_cnt_d (and active_d) describe the next single-token decode step. */
 int lmrl_wordle_tok_accept(lmrl_wordle_tok_ctx *c, const lmrl_wordle_traj *tr, const int32_t *sampled_d, int k,
                            int32_t *next_tok_d, int32_t *next_cnt_d, uint8_t *active_d, int n, void *stream);
+/* One launch for what lies between two LM heads of the lock-step loop: the merge of lmrl_lm_head_sample's partials (called with
+ * LMRL_SAMPLE_KEEP_PARTIALS; sample_ws_d is its workspace, active_d / token_d / logprob_d / pad_token its arguments), lmrl_wordle_tok_accept(k) on
+ * the merged token, and — with m, ws_d (the c = 1 workspace of n envs) and len_d (the session's cache lengths) — the row embeddings of the
+ * single-token forward over (next_tok_d, next_cnt_d) that follows, which is then called with LMRL_FWD_PRE_EMBEDDED.  m = ws_d = len_d = NULL:
+ * no embedding (the action's last token).  One wave per env runs the three kernels' own bodies in their order: every output is bit-identical to
+ * the three launches.  The model must run on the LN-folded path (LMRL_ERR_ARG otherwise). */
+int lmrl_wordle_sample_accept_embed(lmrl_wordle_tok_ctx *c, const lmrl_wordle_traj *tr, const void *sample_ws_d, int vocab_padded, int pad_token,
+                                    const uint8_t *active_d, int32_t *token_d, float *logprob_d, int k, int32_t *next_tok_d, int32_t *next_cnt_d,
+                                    uint8_t *active_out_d, const lmrl_gpt2 *m, void *ws_d, const int32_t *len_d, int n, void *stream);
 /* action tokens -> packed guess for lmrl_wordle_step (+ active mask = episode not done); appends the action to the record */
 int lmrl_wordle_tok_guess(lmrl_wordle_tok_ctx *c, const lmrl_wordle_traj *tr, uint32_t *guess_d, uint8_t *active_d, int n,
                           void *stream);

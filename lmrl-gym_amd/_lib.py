@@ -68,6 +68,11 @@ _SIGS = {
     "lmrl_masked_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lmrl_gather_rows_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_long, c_void_p]),
     "lmrl_gpt2_refresh": (c_int, [c_void_p, c_void_p]),
+    "lmrl_gpt2_pin_prefix": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_uint, c_void_p]),
+    "lmrl_gpt2_unpin_prefix": (c_int, [c_void_p, c_void_p]),
+    "lmrl_gpt2_forward_takes_pre_embedded": (c_int, [c_void_p, c_int, ctypes.c_uint]),
+    "lmrl_wordle_sample_accept_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lmrl_exclusive_scan_i32": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "lmrl_maze_tok_ppo_records": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_void_p] * 10),
     "lmrl_maze_tok_ppo_records_hist": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 10),

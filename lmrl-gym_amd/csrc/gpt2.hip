@@ -24,6 +24,10 @@
 #include <hip/hip_ext.h>
 #include "gemm_dispatch.h"
 #include "skinny_gemm.h"
+#include "embed_stats_core.h"
+#include "sample_reduce_core.h"
+#include "wordle_accept_core.h"
+#include "prefix_pins.h"
 #ifdef LMRL_TOOLS
 #include "ablate_tools.h"
 #endif
@@ -48,6 +52,7 @@ struct Gpt2Model {
     const uint16_t *wte, *wpe;
     const float *lnf_g, *lnf_b;
     Gpt2Layer *layers;
+    PrefixPinList pins;          // lmrl_gpt2_pin_prefix: prefixes that lmrl_gpt2_refresh prefills again
 #ifdef LMRL_TOOLS
     AblateAux ablate_aux;
 #endif
@@ -151,29 +156,33 @@ __global__ __launch_bounds__(256) void embed_stats_kernel(const uint16_t *__rest
     const bool valid = j < cnt[b];
     if (!valid || tok < 0 || tok >= vocab) tok = 0;
     if (!valid || pos >= n_pos) pos = 0;
-    const uint16_t *te = wte + (size_t)tok * d, *pe = wpe + (size_t)pos * d;
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXV; k++) {
-        const int c = (k * 64 + lane) * 4;
-        if (c < d) {
-            const uint2 a = *reinterpret_cast<const uint2 *>(te + c), p = *reinterpret_cast<const uint2 *>(pe + c);
-            const f32x4 v = f32x4{bf16_to_f32((uint16_t)(a.x & 0xffff)) + bf16_to_f32((uint16_t)(p.x & 0xffff)),
-                                  bf16_to_f32((uint16_t)(a.x >> 16)) + bf16_to_f32((uint16_t)(p.x >> 16)),
-                                  bf16_to_f32((uint16_t)(a.y & 0xffff)) + bf16_to_f32((uint16_t)(p.y & 0xffff)),
-                                  bf16_to_f32((uint16_t)(a.y >> 16)) + bf16_to_f32((uint16_t)(p.y >> 16))};
-            *reinterpret_cast<f32x4 *>(x + (size_t)r * d + c) = v;
-            uint2 o;
-            o.x = pack_bf16x2(v[0], v[1]);
-            o.y = pack_bf16x2(v[2], v[3]);
-            *reinterpret_cast<uint2 *>(xb + (size_t)r * d + c) = o;
-            s1 += (v[0] + v[1]) + (v[2] + v[3]);
-            s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-    for (int sl = lane; sl < nslots; sl += 64) stats[(size_t)r * nslots + sl] = sl == 0 ? make_float2(s1, s2) : make_float2(0.f, 0.f);
+    embed_stats_row<MAXV>(wte + (size_t)tok * d, wpe + (size_t)pos * d, x + (size_t)r * d, xb + (size_t)r * d, stats + (size_t)r * nslots, nslots, d, lane);
+}
+
+// Wordle rollout, between two LM heads: sample_reduce_kernel + tok_accept_kernel + embed_stats_kernel (c = 1) of one env in ONE wave — the same
+// three bodies in the same order (sample_reduce_core.h, wordle_accept_core.h, embed_stats_core.h), the token and the next forward's count
+// travelling inside the wave.  No other workgroup's result is read.  EMBED = false: the turn's last token (no forward follows).
+template <int MAXV, bool EMBED>
+__global__ __launch_bounds__(256) void sample_accept_embed_kernel(const float *__restrict__ partials, int np, int pad_token, const uint8_t *active,
+                                                                  int32_t *__restrict__ token, float *__restrict__ logprob, lmrl_wordle_traj tr, int k,
+                                                                  int max_new, int newline, int32_t *__restrict__ next_tok, int32_t *__restrict__ next_cnt,
+                                                                  uint8_t *__restrict__ active_out, const uint16_t *__restrict__ wte,
+                                                                  const uint16_t *__restrict__ wpe, const int32_t *__restrict__ len, float *__restrict__ x,
+                                                                  uint16_t *__restrict__ xb, float2 *__restrict__ stats, int nslots, int B, int d, int vocab,
+                                                                  int n_pos) {
+    const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (e >= B) return;
+    int tok = sample_reduce_row(partials, active, token, logprob, e, np, pad_token, lane);
+    int cnt = 0;
+    if (lane == 0) cnt = wordle_accept_env(tr, e, tok, k, max_new, newline, next_tok, next_cnt, active_out);
+    if (!EMBED) return;
+    tok = __shfl(tok, 0); cnt = __shfl(cnt, 0);
+    // embed_stats_kernel's row e of a c = 1 forward over (next_tok, next_cnt): rows without a new token embed (token 0, position 0)
+    int pos = len[e];
+    const bool valid = cnt > 0;
+    if (!valid || tok < 0 || tok >= vocab) tok = 0;
+    if (!valid || pos >= n_pos) pos = 0;
+    embed_stats_row<MAXV>(wte + (size_t)tok * d, wpe + (size_t)pos * d, x + (size_t)e * d, xb + (size_t)e * d, stats + (size_t)e * nslots, nslots, d, lane);
 }
 
 // ------------------------------------------------------------------------------------------ fused small kernels
@@ -1149,6 +1158,37 @@ lmrl_gpt2 *lmrl_gpt2_create(const lmrl_gpt2_config *cfg, const void *wte, const 
     return m;
 }
 
+// The forward's path choices, in one place each (gpt2_forward_impl and lmrl_gpt2_forward_takes_pre_embedded read the same ones)
+static bool fwd_ln_folded(const lmrl_gpt2_config &cf, unsigned flags) {
+    return !(flags & LMRL_FWD_LN_STANDALONE) && g_gemm_variant != 1 && ln_fusion_nq(cf.d_model) != 0;
+}
+static bool fwd_ragged(const lmrl_gpt2_config &cf, int M, unsigned flags, bool all_hidden) {
+    return fwd_ln_folded(cf, flags) && !all_hidden && !(flags & LMRL_FWD_RAGGED_NEVER) && ((flags & LMRL_FWD_RAGGED_ALWAYS) || M >= kRaggedAutoMinSlots);
+}
+// a single-token forward of b envs (no all_hidden, no attached prefix) with these flags reads pre-written row embeddings
+static bool fwd_takes_pre_embedded(const lmrl_gpt2_config &cf, int b, unsigned flags) {
+    return fwd_ln_folded(cf, flags) && !fwd_ragged(cf, b, flags, false) && !(flags & LMRL_FWD_SKINNY);
+}
+
+static int gpt2_forward_impl(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, const int32_t *tokens_d, const int32_t *cnt_d,
+                             int32_t *len_d, int b, int c, void *last_hidden_d, void *all_hidden_d, const lmrl_kv_prefix *pfx, unsigned flags,
+                             void *stream);
+
+// The device side of prefix_pins.h: exactly what a 1-env KVSession of these buffers does for reset() + forward(chunk of 8) per chunk.  The
+// chunk's count word lives in the workspace's per-env index slot, which no forward reads.
+struct PinOps {
+    lmrl_gpt2 *m; void *stream;
+    int zero_len(const PrefixPin &p) {
+        LMRL_CHECK_HIP(hipMemsetAsync(p.len_d, 0, sizeof(int32_t), as_stream(stream)));
+        return LMRL_OK;
+    }
+    int forward_chunk(const PrefixPin &p, const int32_t *tokens_d, int n) {
+        Gpt2Ws w; w.carve(p.ws_d, m->cfg, kPinChunk, 1);
+        LMRL_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)w.rows_idx, n, 1, as_stream(stream)));
+        return gpt2_forward_impl(m, p.kv_d, p.tmax, p.ws_d, tokens_d, w.rows_idx, p.len_d, 1, kPinChunk, p.last_hidden_d, nullptr, nullptr, p.flags, stream);
+    }
+};
+
 int lmrl_gpt2_refresh(lmrl_gpt2 *m, void *stream) {
     LMRL_REQUIRE(m && m->layers, "lmrl_gpt2_refresh: bad argument");
     const int d = m->cfg.d_model, dff = m->cfg.d_ff;
@@ -1160,11 +1200,35 @@ int lmrl_gpt2_refresh(lmrl_gpt2 *m, void *stream) {
                            L.bf_fc, dff, d);
     }
     LMRL_CHECK_LAUNCH();
+    // the pinned prefixes are derived from the weights too: prefill them again, behind the fold kernels
+    PinOps ops{m, stream};
+    return prefix_pins_refresh(m->pins, ops);
+}
+
+int lmrl_gpt2_pin_prefix(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, const int32_t *tokens_d, int n_tokens, int32_t *len_d,
+                         void *last_hidden_d, unsigned flags, void *stream) {
+    LMRL_REQUIRE(m && m->layers, "lmrl_gpt2_pin_prefix: bad argument");
+    LMRL_REQUIRE(!(flags & LMRL_FWD_PRE_EMBEDDED), "lmrl_gpt2_pin_prefix: LMRL_FWD_PRE_EMBEDDED is a per-call promise, not a session flag");
+    const PrefixPin p{kv_d, tmax, ws_d, tokens_d, n_tokens, len_d, last_hidden_d, flags};
+    if (const char *why = m->pins.add(p)) {
+        set_error("lmrl_gpt2_pin_prefix: %s", why);
+        return LMRL_ERR_ARG;
+    }
+    PinOps ops{m, stream};
+    const int rc = prefix_pin_prefill(p, ops);
+    if (rc != LMRL_OK) m->pins.remove(kv_d);
+    return rc;
+}
+
+int lmrl_gpt2_unpin_prefix(lmrl_gpt2 *m, const void *kv_d) {
+    LMRL_REQUIRE(m, "lmrl_gpt2_unpin_prefix: bad argument");
+    LMRL_REQUIRE(m->pins.remove(kv_d), "lmrl_gpt2_unpin_prefix: this cache is not pinned");
     return LMRL_OK;
 }
 
 void lmrl_gpt2_destroy(lmrl_gpt2 *m) {
     if (!m) return;
+    m->pins.clear();
     for (int l = 0; m->layers && l < m->cfg.n_layer; l++) {
         Gpt2Layer &L = m->layers[l];
         (void)hipFree(L.wf_qkv); (void)hipFree(L.cs_qkv); (void)hipFree(L.bf_qkv);
@@ -1207,7 +1271,7 @@ static int gpt2_forward_impl(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, con
     if (unsigned long long *ctr = prof_byte_counter(c == 1 ? PROF_ATTN_DECODE : PROF_ATTN_CHUNK))
         hipLaunchKernelGGL(attn_bytes_kernel, dim3(1), dim3(256), 0, s, cnt_d, len_d, b, c, cf.n_head * cf.n_layer, ctr, c == 1 ? n_shared : 0);
     LMRL_REQUIRE(!((flags & LMRL_FWD_RAGGED_ALWAYS) && (flags & LMRL_FWD_RAGGED_NEVER)), "lmrl_gpt2_forward: contradictory ragged flags");
-    const bool fused = !(flags & LMRL_FWD_LN_STANDALONE) && g_gemm_variant != 1 && ln_fusion_nq(d) != 0;
+    const bool fused = fwd_ln_folded(cf, flags);
     // Bits >= 16 of `flags` are reserved.  Only the -DLMRL_TOOLS build (`python lmrl-gym_amd/build.py --tools` -> liblmrl_amd_tools.so, loaded by
     // tools/bench_ablate_decode.py alone) gives them a meaning: timing-only launch ablations of the single-token decode layers whose RESULTS ARE
     // GARBAGE (csrc/ablate_tools.h).  The product library refuses them.
@@ -1222,7 +1286,7 @@ static int gpt2_forward_impl(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, con
     }
     hipStream_t aux_stream = aux.stream; hipEvent_t aux_fork = aux.fork, aux_join = aux.join;
 #else
-    LMRL_REQUIRE(((flags & ~LMRL_FWD_SKINNY) >> 16) == 0u, "lmrl_gpt2_forward: flag bits 16-29 are reserved (launch ablations exist only in the LMRL_TOOLS build)");
+    LMRL_REQUIRE(((flags & ~(LMRL_FWD_SKINNY | LMRL_FWD_PRE_EMBEDDED)) >> 16) == 0u, "lmrl_gpt2_forward: flag bits 16-29 are reserved (launch ablations exist only in the LMRL_TOOLS build)");
 #define LMRL_ABL(bit) false
     constexpr hipStream_t aux_stream = nullptr; constexpr hipEvent_t aux_fork = nullptr, aux_join = nullptr;   // dead branches below still parse
     (void)aux_stream; (void)aux_fork; (void)aux_join;
@@ -1231,15 +1295,19 @@ static int gpt2_forward_impl(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, con
     // ragged batches (LN-folded path, unless the caller wants every row's hidden state back): by default only the forwards of
     // large batches qualify (b*c >= 2048); LMRL_FWD_RAGGED_ALWAYS compacts every forward (generation loops whose rows finish at
     // different steps), LMRL_FWD_RAGGED_NEVER none.  A per-call property: nothing here is process state.
-    const bool ragged = fused && !all_hidden_d && !(flags & LMRL_FWD_RAGGED_NEVER) &&
-                        ((flags & LMRL_FWD_RAGGED_ALWAYS) || M >= kRaggedAutoMinSlots);
+    const bool ragged = fwd_ragged(cf, M, flags, all_hidden_d != nullptr);
     const int32_t *off = ragged ? w.off : nullptr, *row_map = ragged ? w.row_map : nullptr, *m_dev = ragged ? w.off + b : nullptr;
     if (ragged) hipLaunchKernelGGL(ragged_scan_kernel, dim3(1), dim3(1024), 0, s, cnt_d, b, c, w.off, w.row_map);
     auto ln = [&](const float *g, const float *be, uint16_t *y, const int32_t *idx, int rows) {
         if (d <= 1024) hipLaunchKernelGGL(layernorm_kernel<4>, dim3(ceil_div(rows, 4)), dim3(256), 0, s, w.x, g, be, y, idx, rows, d, cf.ln_eps);
         else hipLaunchKernelGGL(layernorm_kernel<8>, dim3(ceil_div(rows, 4)), dim3(256), 0, s, w.x, g, be, y, idx, rows, d, cf.ln_eps);
     };
-    if (fused) {
+    const bool pre_embedded = (flags & LMRL_FWD_PRE_EMBEDDED) != 0u;
+    LMRL_REQUIRE(!pre_embedded || (c == 1 && !pfx && !all_hidden_d && fwd_takes_pre_embedded(cf, b, flags)),
+                 "lmrl_gpt2_forward: LMRL_FWD_PRE_EMBEDDED needs a single-token forward on the LN-folded path (not ragged, skinny or prefixed)");
+    if (pre_embedded) {
+        // w.x, w.h and stats slot 0 of every row were written by lmrl_wordle_sample_accept_embed for these tokens_d / cnt_d
+    } else if (fused) {
         // LN-folded path: w.h holds the bf16 copy of the residual stream, w.stats its per-row (sum, sum^2) slots
         if (d <= 1024) hipLaunchKernelGGL(embed_stats_kernel<4>, dim3(ceil_div(M, 4)), dim3(256), 0, s, m->wte, m->wpe, tokens_d, cnt_d, len_d,
                                           w.x, w.h, w.stats, nsl, b, c, d, cf.vocab, cf.n_pos, row_map, m_dev);
@@ -1460,10 +1528,47 @@ int lmrl_gpt2_forward(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, const int3
     return gpt2_forward_impl(m, kv_d, tmax, ws_d, tokens_d, cnt_d, len_d, b, c, last_hidden_d, all_hidden_d, nullptr, flags, stream);
 }
 
+int lmrl_gpt2_forward_takes_pre_embedded(const lmrl_gpt2 *m, int b, unsigned flags) {
+    return (m && b > 0 && fwd_takes_pre_embedded(m->cfg, b, flags & ~LMRL_FWD_PRE_EMBEDDED)) ? 1 : 0;
+}
+
 int lmrl_gpt2_forward_prefixed(lmrl_gpt2 *m, void *kv_d, int tmax, void *ws_d, const int32_t *tokens_d, const int32_t *cnt_d,
                                int32_t *len_d, int b, void *last_hidden_d, const lmrl_kv_prefix *pfx, unsigned flags, void *stream) {
     LMRL_REQUIRE(pfx, "lmrl_gpt2_forward_prefixed: no prefix");
     return gpt2_forward_impl(m, kv_d, tmax, ws_d, tokens_d, cnt_d, len_d, b, 1, last_hidden_d, nullptr, pfx, flags, stream);
+}
+
+int lmrl_wordle_sample_accept_embed(lmrl_wordle_tok_ctx *c, const lmrl_wordle_traj *tr, const void *sample_ws_d, int vocab_padded, int pad_token,
+                                    const uint8_t *active_d, int32_t *token_d, float *logprob_d, int k, int32_t *next_tok_d, int32_t *next_cnt_d,
+                                    uint8_t *active_out_d, const lmrl_gpt2 *m, void *ws_d, const int32_t *len_d, int n, void *stream) {
+    LMRL_REQUIRE(c && tr && sample_ws_d && token_d && next_tok_d && next_cnt_d && n > 0 && k >= 0 && k < c->max_new,
+                 "lmrl_wordle_sample_accept_embed: bad argument");
+    LMRL_REQUIRE(vocab_padded > 0 && vocab_padded % kPartialTileCols == 0, "lmrl_wordle_sample_accept_embed: bad vocab_padded");
+    LMRL_REQUIRE((m != nullptr) == (ws_d != nullptr) && (m != nullptr) == (len_d != nullptr),
+                 "lmrl_wordle_sample_accept_embed: model, workspace and cache lengths come together (all null: no embedding)");
+    const float *partials = (const float *)sample_ws_d;
+    const int np = vocab_padded / kPartialTileCols;
+    const dim3 grid(ceil_div(n, 4)), block(256);
+    hipStream_t s = as_stream(stream);
+    if (!m) {
+        hipLaunchKernelGGL((sample_accept_embed_kernel<4, false>), grid, block, 0, s, partials, np, pad_token, active_d, token_d, logprob_d, *tr, k, c->max_new,
+                           c->t.newline, next_tok_d, next_cnt_d, active_out_d, (const uint16_t *)nullptr, (const uint16_t *)nullptr, (const int32_t *)nullptr,
+                           (float *)nullptr, (uint16_t *)nullptr, (float2 *)nullptr, 0, n, 0, 0, 0);
+    } else {
+        const lmrl_gpt2_config &cf = m->cfg;
+        LMRL_REQUIRE(fwd_ln_folded(cf, 0u), "lmrl_wordle_sample_accept_embed: this model's forwards do not run on the LN-folded path");
+        LMRL_REQUIRE(vocab_padded == cf.vocab_padded, "lmrl_wordle_sample_accept_embed: vocab_padded is not the model's");
+        Gpt2Ws w; w.carve(ws_d, cf, n, n);          // the workspace of the c = 1 forward that follows
+        const int nsl = Gpt2Ws::nslots(cf);
+        if (cf.d_model <= 1024)
+            hipLaunchKernelGGL((sample_accept_embed_kernel<4, true>), grid, block, 0, s, partials, np, pad_token, active_d, token_d, logprob_d, *tr, k, c->max_new,
+                               c->t.newline, next_tok_d, next_cnt_d, active_out_d, m->wte, m->wpe, len_d, w.x, w.h, w.stats, nsl, n, cf.d_model, cf.vocab, cf.n_pos);
+        else
+            hipLaunchKernelGGL((sample_accept_embed_kernel<8, true>), grid, block, 0, s, partials, np, pad_token, active_d, token_d, logprob_d, *tr, k, c->max_new,
+                               c->t.newline, next_tok_d, next_cnt_d, active_out_d, m->wte, m->wpe, len_d, w.x, w.h, w.stats, nsl, n, cf.d_model, cf.vocab, cf.n_pos);
+    }
+    LMRL_CHECK_LAUNCH();
+    return LMRL_OK;
 }
 
 int lmrl_gpt2_kv_attach(const lmrl_gpt2 *m, int src_b, const int32_t *src_len_d, const void *src_hidden_d, const int32_t *idx_d, int b,

@@ -20,6 +20,7 @@
 #include <atomic>
 #include "gemm_dispatch.h"
 #include "threefry.h"
+#include "sample_reduce_core.h"
 
 namespace lmrl {
 
@@ -91,13 +92,12 @@ __device__ __forceinline__ unsigned long long tile_mass_rescaled(unsigned long l
     return (unsigned long long)((double)s_t * (double)__expf((tmax - rmax) * inv_t));
 }
 
-constexpr int kPartialFloats = 6;   // {max, sumexp, best_score, best_col, best_z, pad}
-
 // LM head:   z[m][n] = (h[m] . wte[n])   (+ ILQL perturbation, + steer), then the sampling epilogue on z / T.
 // One 128 x 128 tile per 8-wave workgroup (2 x 4 waves, 64 x 32 outputs each) on the large-tile main loop of gemm8_bf16.h, two
 // workgroups per CU; up to three GEMM passes over the same output tile (pi, q1, q2) combined in registers.  The four column-quarter
 // waves of a row merge their partials through LDS so exactly one partial per (row, 128-column tile) reaches HBM.
 constexpr int kLmBM = 128, kLmBN = 128, kLmWM = 2, kLmWN = 4, kLmStages = 2;
+static_assert(kLmBN == kPartialTileCols, "one partial per (row, LM-head tile): sample_reduce_core.h");
 // The Q-head forms (two or three products per tile, three accumulator sets: 173 VGPRs) fit ONE workgroup per CU whatever the ring — so they take a
 // 4-slot ring (128 KB of the CU's 160 KB LDS): three stages in flight behind the one being consumed instead of one (round 6)
 #ifdef LMRL_LM_Q_STAGES
@@ -581,34 +581,7 @@ __global__ __launch_bounds__(256) void sample_reduce_kernel(const float *__restr
                                                             int M, int np, int pad_token) {
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (m >= M) return;
-    if (active && !active[m]) {
-        if (lane == 0) { token[m] = pad_token; if (logprob) logprob[m] = 0.f; }
-        return;
-    }
-    float pmax = -INFINITY, psum = 0.f, best = -INFINITY, best_z = 0.f;
-    int best_col = 0x7fffffff;
-    for (int t = lane; t < np; t += 64) {
-        const float *p = partials + ((size_t)m * np + t) * kPartialFloats;
-        const float om = p[0], os = p[1], ob = p[2], oz = p[4];
-        const int oc = __float_as_int(p[3]);
-        const float nm = fmaxf(pmax, om);
-        const float e1 = (pmax == -INFINITY) ? 0.f : __expf(pmax - nm), e2 = (om == -INFINITY) ? 0.f : __expf(om - nm);
-        psum = psum * e1 + os * e2; pmax = nm;
-        if (ob > best || (ob == best && oc < best_col)) { best = ob; best_col = oc; best_z = oz; }
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float om = __shfl_xor(pmax, o), os = __shfl_xor(psum, o), ob = __shfl_xor(best, o), oz = __shfl_xor(best_z, o);
-        const int oc = __shfl_xor(best_col, o);
-        const float nm = fmaxf(pmax, om);
-        const float e1 = (pmax == -INFINITY) ? 0.f : __expf(pmax - nm), e2 = (om == -INFINITY) ? 0.f : __expf(om - nm);
-        psum = psum * e1 + os * e2; pmax = nm;
-        if (ob > best || (ob == best && oc < best_col)) { best = ob; best_col = oc; best_z = oz; }
-    }
-    if (lane == 0) {
-        token[m] = best_col;
-        if (logprob) logprob[m] = best_z - (pmax + __logf(psum));
-    }
+    (void)sample_reduce_row(partials, active, token, logprob, m, np, pad_token, lane);
 }
 
 // ---- top-k sampling over materialised logits: one workgroup per row.
@@ -1432,6 +1405,9 @@ int lmrl_lm_head_sample(const void *hidden_d, const void *wte_d, const void *q_h
     const bool nucleus = p->top_p > 0.f && p->top_p < 1.f && !sp.greedy;
     const bool topk_on = p->top_k > 0 && p->top_k < vocab;
     const bool nuc_only = nucleus && !topk_on;
+    // LMRL_SAMPLE_KEEP_PARTIALS: only where the plain partials are what the call leaves behind — never a silent change of path
+    LMRL_REQUIRE(!(p->flags & LMRL_SAMPLE_KEEP_PARTIALS) || (nops == 1 && !nucleus && !topk_on && (sp.greedy || p->rng == LMRL_RNG_PHILOX)),
+                 "lmrl_lm_head_sample: LMRL_SAMPLE_KEEP_PARTIALS needs policy-only Philox / greedy sampling without top_k / top_p");
     bool topc = false;
     int32_t *fb = nullptr;
     const uint16_t *A0 = (const uint16_t *)hidden_d, *W0 = (const uint16_t *)wte_d;
@@ -1524,7 +1500,7 @@ int lmrl_lm_head_sample(const void *hidden_d, const void *wte_d, const void *q_h
     else if ((p->top_k > 0 && p->top_k < vocab) || nucleus) {
         LMRL_REQUIRE(logits_out_d, "lmrl_lm_head_sample: top_k / top_p sampling needs logits_out_d (materialised logits)");
         launch_topk_sample(logits_out_d, vocab_padded, m, vocab, p->top_k, p->top_p, active_d, token_d, logprob_d, sp, p->pad_token, s);
-    } else {
+    } else if (!(p->flags & LMRL_SAMPLE_KEEP_PARTIALS)) {      // else: the caller merges the partials (lmrl_wordle_sample_accept_embed)
         hipLaunchKernelGGL(sample_reduce_kernel, dim3(ceil_div(m, 4)), dim3(256), 0, s, partials, active_d, token_d, logprob_d, m,
                            vocab_padded / kLmBN, p->pad_token);
     }

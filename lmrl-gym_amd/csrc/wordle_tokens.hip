@@ -15,14 +15,9 @@
 // One thread per env; all arrays struct-of-arrays / row-per-env int32, tiny next to the model traffic.
 #include "../../include/lmrl_amd.h"
 #include "common.h"
+#include "wordle_accept_core.h"
 
 namespace lmrl {
-
-struct WordleTokCtx {
-    lmrl_wordle_tokens t;
-    uint32_t *cls_d = nullptr;   // [vocab] token classes
-    int vocab = 0, max_new = 0, cap = 0;
-};
 
 // token class word: bits 0-24 up to five 5-bit letters, 25-27 letter count (7 = token makes the action invalid),
 // bit 28 whitespace other than ' ' before the first letter (or anywhere if no letters), bit 29 ... after the last letter
@@ -52,16 +47,7 @@ __global__ void tok_accept_kernel(lmrl_wordle_tokens t, lmrl_wordle_traj tr, con
                                   int32_t *next_tok, int32_t *next_cnt, uint8_t *active_out, int n) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    int cnt = 0;
-    if (tr.gen_active[e]) {
-        const int tok = sampled[e];
-        tr.gen[(size_t)e * max_new + k] = tok;
-        tr.gen_len[e] = k + 1;
-        if (tok == t.newline || k + 1 >= max_new) tr.gen_active[e] = 0;   // eos reached or max_new_tokens
-        else { cnt = 1; next_tok[e] = tok; }
-    }
-    next_cnt[e] = cnt;
-    if (active_out) active_out[e] = (uint8_t)cnt;
+    (void)wordle_accept_env(tr, e, sampled[e], k, max_new, t.newline, next_tok, next_cnt, active_out);
 }
 
 // decode the generated ids into a packed guess; append the action tokens (+ forced '\n') to the trajectory
@@ -158,8 +144,6 @@ __global__ void tok_steer_kernel(lmrl_wordle_tokens t, const uint32_t *scripted_
 }  // namespace lmrl
 
 using namespace lmrl;
-
-struct lmrl_wordle_tok_ctx : public WordleTokCtx {};
 
 extern "C" {
 

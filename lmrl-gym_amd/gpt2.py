@@ -65,6 +65,7 @@ class SampleParams(ctypes.Structure):
 
 RNG_PHILOX, RNG_JAX = 0, 1       # lmrl_sample_params.rng
 SAMPLE_WANT_LOGITS = 1           # lmrl_sample_params.flags: materialise logits_out even where the fused top-k path would not
+SAMPLE_KEEP_PARTIALS = 2         # ... leave the per-tile partials in the workspace, launch no reduce (`KVSession.sample(keep_partials=True)`)
 
 
 class _CKVPrefix(ctypes.Structure):      # lmrl_kv_prefix (include/lmrl_amd.h)
@@ -131,8 +132,10 @@ class GPT2Engine:
         """Overwrite this engine's weights IN PLACE from a parameter dict of the same architecture (HF names; fp32 masters of a trainer,
         device or host) — the online loops' `policy.set_params(train_state.params)` after every round (llm_rl_scripts/wordle/ppo/
         train_ppo_gpt2.py via LLM_RL/algorithms/ppo/train.py) without a host round trip or a new engine: device-to-device copies with the
-        bf16 rounding / [out][in] layout of `__init__`, then the LayerNorm-folded copies are re-derived (`lmrl_gpt2_refresh`).  Sessions, KV
-        caches and captured hipGraphs of this engine stay valid (same addresses)."""
+        bf16 rounding / [out][in] layout of `__init__`, then everything the engine derives from the weights is derived again on the current
+        stream (`lmrl_gpt2_refresh`): the LayerNorm-folded copies and the K/V rows of every pinned prefix (`KVSession.pin_as_prefix`).
+        Sessions, KV caches and captured hipGraphs of this engine stay valid (same addresses); work on other streams has to be ordered behind
+        this call like behind any other weight write."""
         cfg = self.cfg
         sd = {k[len("transformer."):] if k.startswith("transformer.") else k: v for k, v in params.items()}
         self.wte[: cfg.vocab].copy_(sd["wte.weight"][: cfg.vocab])
@@ -193,6 +196,7 @@ class GPT2Engine:
 FWD_LN_STANDALONE, FWD_RAGGED_ALWAYS, FWD_RAGGED_NEVER, FWD_ATTN_VALU, FWD_KV_FROM_GEMM, FWD_FULL_LAST_LAYER = 1, 2, 4, 8, 16, 32
 FWD_ATTN_ITEMS2, FWD_ATTN_ITEMS3 = 64, 128
 FWD_SKINNY = 1 << 30       # decode forwards of <= 16 sequences on the skinny-M Dense kernels (csrc/skinny_gemm.h)
+FWD_PRE_EMBEDDED = 1 << 31 # per call, never a session flag: the row embeddings are already in the workspace (`KVSession.forward(pre_embedded=True)`)
 
 
 class KVSession:
@@ -211,7 +215,49 @@ class KVSession:
         self.token = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.logprob = torch.zeros(batch, dtype=torch.float32, device=dev)
 
+    _pinned = 0      # tokens of the prefix this (1-env) session holds as a pinned prefix of its engine (pin_as_prefix); 0: not pinned
+
+    def pin_as_prefix(self, tokens) -> int:
+        """This 1-env session becomes a PINNED prefix of its engine (`lmrl_gpt2_pin_prefix`): its cache is prefilled once with `tokens` (ints,
+        8 per forward, this session's flags — the launches of reset() + forward(chunk of 8) per 8 tokens, bit-identical rows) and the engine
+        prefills it again whenever its weights change (`GPT2Engine.load_params` -> `lmrl_gpt2_refresh`).  Consumers only copy out of it
+        (`broadcast_prefix_from`), also inside captured graphs.  Do not forward through or reset a pinned session; `unpin_prefix` releases it
+        (done when the session is collected).  Returns the prefix length."""
+        import torch
+        if self.B != 1:
+            raise _lib.LmrlError("pin_as_prefix: a pinned prefix is a 1-env session")
+        if self._pinned:      # the engine holds the addresses of this pin's buffers: nothing of it may be replaced while it stands
+            raise _lib.LmrlError("pin_as_prefix: this session is already pinned (unpin_prefix() it first)")
+        toks = [int(t) for t in tokens]
+        e = self.eng
+        pin_tokens = torch.zeros(-(-max(len(toks), 1) // 8) * 8, dtype=torch.int32, device=e.device)
+        pin_tokens[: len(toks)] = torch.tensor(toks, dtype=torch.int32)
+        self.reset()
+        # (a prefill that fails leaves no pin behind in the library, so `pin_tokens` may go away with this frame)
+        _lib.check(e._L.lmrl_gpt2_pin_prefix(e._h, _lib.ptr(self.kv), self.tmax, _lib.ptr(self.ws[8]), _lib.ptr(pin_tokens), len(toks),
+                                             _lib.ptr(self.len), _lib.ptr(self.last_hidden), self.flags, _lib.stream_ptr()), "lmrl_gpt2_pin_prefix")
+        self._pin_tokens = pin_tokens
+        self._pinned = self._len_bound = len(toks)
+        return self._pinned
+
+    def _refuse_if_pinned(self, what: str):
+        if self._pinned:
+            raise _lib.LmrlError(f"{what}: this session is a pinned prefix of its engine, which prefills it itself (unpin_prefix() it first)")
+
+    def unpin_prefix(self):
+        if self._pinned:
+            self._pinned = 0
+            _lib.check(self.eng._L.lmrl_gpt2_unpin_prefix(self.eng._h, _lib.ptr(self.kv)), "lmrl_gpt2_unpin_prefix")
+
+    def __del__(self):
+        try:      # the engine must not keep addresses of buffers that are about to be freed
+            if self._pinned and self.eng._h:
+                self.unpin_prefix()
+        except Exception:
+            pass
+
     def reset(self):
+        self._refuse_if_pinned("reset")
         self.len.zero_()
         self._len_bound = 0
         self.shared_prefix = 0
@@ -221,6 +267,7 @@ class KVSession:
         """Truncate / set every env's cache length from the host (int array [B]): positions >= lens[b] are treated as free and will be
         overwritten by the next forwards — how a policy keeps the K/V rows of the longest common prefix of consecutive prompts."""
         import torch
+        self._refuse_if_pinned("set_len")
         lens = np.ascontiguousarray(lens, dtype=np.int32)
         assert lens.shape == (self.B,) and int(lens.max(initial=0)) <= self.tmax
         self.len.copy_(torch.from_numpy(lens))
@@ -234,10 +281,15 @@ class KVSession:
 
     _prefix = None   # (_CKVPrefix, keep-alive refs) while the envs stand on rows of a prompt-prefix session (attach_prefix_from)
 
-    def forward(self, tokens, cnt, chunk: int, all_hidden=None, len_bound_after: Optional[int] = None):
+    def forward(self, tokens, cnt, chunk: int, all_hidden=None, len_bound_after: Optional[int] = None, pre_embedded: bool = False):
         """tokens int32 [B*chunk], cnt int32 [B]; updates the cache, self.len and self.last_hidden.  `len_bound_after`: the caller's exact
-        knowledge of max(len) after this forward (ragged prefills); default: the previous bound + chunk."""
+        knowledge of max(len) after this forward (ragged prefills); default: the previous bound + chunk.  `pre_embedded` (chunk 1): the rows'
+        embeddings are already in this session's workspace (`lmrl_wordle_sample_accept_embed` wrote them for these tokens / cnt); the library
+        refuses the promise where the forward would not read them (not the LN-folded path, ragged, skinny, prefixed)."""
         e = self.eng
+        self._refuse_if_pinned("forward")
+        if pre_embedded and (chunk != 1 or self._prefix is not None):
+            raise _lib.LmrlError("pre_embedded: single-token forwards of a session without an attached prefix only")
         self._len_bound = self._len_bound + chunk if len_bound_after is None else int(len_bound_after)
         if self._len_bound > self.tmax:
             raise _lib.LmrlError(f"KV cache overflow: up to {self._len_bound} positions would be written into a cache of tmax = {self.tmax} "
@@ -251,7 +303,8 @@ class KVSession:
             return self.last_hidden
         _lib.check(e._L.lmrl_gpt2_forward(e._h, _lib.ptr(self.kv), self.tmax, _lib.ptr(self.ws[chunk]), _lib.ptr(tokens),
                                           _lib.ptr(cnt), _lib.ptr(self.len), self.B, chunk, _lib.ptr(self.last_hidden),
-                                          _lib.ptr(all_hidden), self.flags | ((self.shared_prefix & 0xFF) << 8), _lib.stream_ptr()), "lmrl_gpt2_forward")
+                                          _lib.ptr(all_hidden), self.flags | ((self.shared_prefix & 0xFF) << 8) | (FWD_PRE_EMBEDDED if pre_embedded else 0),
+                                          _lib.stream_ptr()), "lmrl_gpt2_forward")
         return self.last_hidden
 
     def broadcast_prefix_from(self, src: "KVSession", n_pos: int):
@@ -301,15 +354,21 @@ class KVSession:
         self.shared_prefix = 0
 
     def sample(self, params: SampleParams, steer_tok=None, active=None, hidden=None, logits_out=None,
-               q1=None, q2=None, want_logprob: bool = True):
+               q1=None, q2=None, want_logprob: bool = True, keep_partials: bool = False):
         """Fused LM head + sampling of one token per env from `hidden` (default: last_hidden).
         logits_out: with 0 < top_k <= 256 and / or 0 < top_p < 1 the call keeps candidates, not logits (logits_out is then only scratch for rows
         handed back to the materialised selection); set `params.flags = SAMPLE_WANT_LOGITS` to have the logits written there as well.
         q1/q2: optional (q_hidden bf16 [B][d], w bf16 [Vp][d], bias f32 [Vp]) ILQL operands.
         want_logprob=False skips the log-sum-exp over the vocabulary (the reference's sampling step returns only the token;
-        rollouts do not use the sampled token's log-probability) and returns (token, None)."""
+        rollouts do not use the sampled token's log-probability) and returns (token, None).
+        keep_partials: the LM head only — its per-tile partials stay in `self.sample_ws` for `lmrl_wordle_sample_accept_embed`, which merges
+        them into `self.token` (and `self.logprob`); nothing is written to them here.  `want_logprob` still decides whether the partials
+        carry the log-sum-exp pieces: hand that entry `self.logprob` exactly when it is True."""
         e = self.eng
         h = self.last_hidden if hidden is None else hidden
+        if keep_partials:      # on a copy: the caller's struct keeps its flags for its next call
+            params = SampleParams.from_buffer_copy(params)
+            params.flags |= SAMPLE_KEEP_PARTIALS
         qa = [None] * 6
         if q1 is not None:
             qa[0:3] = [_lib.ptr(x) for x in q1]

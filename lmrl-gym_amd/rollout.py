@@ -152,8 +152,12 @@ class WordleRolloutEngine:
     def __init__(self, engine: GPT2Engine, vocab: W.Vocabulary, batch: int, tokens: Optional[WordleTokenTable] = None,
                  max_new_tokens: int = 6, require_words_in_vocab: bool = True, bad_word_reward: float = -10.0,
                  traj_cap: int = 128, share_header: bool = True, value_engine: Optional[GPT2Engine] = None, q1_head: Optional[dict] = None,
-                 q2_head: Optional[dict] = None, beta: float = 0.0, session_flags: int = 0):
+                 q2_head: Optional[dict] = None, beta: float = 0.0, session_flags: int = 0, pin_header: bool = True, fused_tail: bool = True):
         """`session_flags`: lmrl_gpt2_forward variants (gpt2.FWD_*) of this engine's KV sessions (A/B hooks; results are bit-identical).
+        `pin_header` (with `share_header`, bf16 engine): the shared header's K/V rows are a PINNED prefix of the engine (`KVSession.pin_as_prefix`) —
+        prefilled here once and again by every `load_params` — and an episode only broadcasts them; False restores the prefill inside every
+        episode.  `fused_tail`: reduce + accept + embed between two LM heads as one launch (`lmrl_wordle_sample_accept_embed`) wherever
+        `_fused_tail_ok` holds; False keeps the three launches.  Both switches leave every output bit for bit as it is.
         `value_engine` + `q1_head` (+ `q2_head`) + `beta` turn the policy into the ILQL value policy
         (`GPT2ValueRLGeneration`, value_rl_base/gpt2/generation.py:97-119): `engine` is pi_beta, `value_engine` the value base
         whose last hidden state feeds the Q heads (`policies.heads_to_engine_layout(..., engine=engine)` dicts); logits = pi_beta + beta * min(Q1, Q2)
@@ -168,7 +172,8 @@ class WordleRolloutEngine:
         self.eng, self.vocab, self.B = engine, vocab, batch
         self._twin_args = dict(tokens=tokens, max_new_tokens=max_new_tokens, require_words_in_vocab=require_words_in_vocab,
                                bad_word_reward=bad_word_reward, traj_cap=traj_cap, share_header=share_header, value_engine=value_engine,
-                               q1_head=q1_head, q2_head=q2_head, beta=beta, session_flags=session_flags)
+                               q1_head=q1_head, q2_head=q2_head, beta=beta, session_flags=session_flags, pin_header=pin_header,
+                               fused_tail=fused_tail)
         self._lanes = None           # text_env_eval(concurrent=n): [(engine, stream)], this engine first
         self.episodes = 0            # eager episodes run by text_env_eval over this engine's life: part of the sampler stream key
         # the pad id is the first id AFTER the policy's vocabulary, as in the reference: the task scripts add `<|pad|>` to the tokenizer (id 50257,
@@ -181,8 +186,10 @@ class WordleRolloutEngine:
         self.env = W.VectorWordleEnv(vocab, require_words_in_vocab, bad_word_reward)
         self.env._alloc(batch)
         self.ses = engine.session(batch, traj_cap, int(session_flags))
-        # every env starts from the same header text: its K/V are computed once per episode on a 1-env session and broadcast
+        # every env starts from the same header text: its K/V are computed on a 1-env session (once, as a pinned prefix of the engine, or once
+        # per episode) and broadcast
         self.share_header = share_header
+        self.session_flags, self.fused_tail = int(session_flags), bool(fused_tail)
         self.ses1 = engine.session(1, 16) if share_header else None
         self.veng, self.q1, self.q2, self.beta = value_engine, q1_head, q2_head, float(beta)
         assert (value_engine is None) == (q1_head is None), "value_engine and q1_head come together"
@@ -193,6 +200,11 @@ class WordleRolloutEngine:
             self._aux_stream = _t.cuda.Stream(device=self.dev)
             self._ev_fork, self._ev_join = _t.cuda.Event(), _t.cuda.Event()
         self.vses1 = value_engine.session(1, 16) if value_engine is not None and share_header else None
+        self.pin_header = bool(pin_header) and share_header and hasattr(self.ses1, "pin_as_prefix")
+        if self.pin_header:       # lane twins (`_eval_lanes`) come through here too: every lane pins its own session
+            self.ses1.pin_as_prefix(self.tokens.header)
+            if self.vses1 is not None:
+                self.vses1.pin_as_prefix(self.tokens.header)
         # the Q heads' dense1 outputs (and its split-K workspace on an fp32 value base): this engine's own, never shared with a lane twin
         self.qh = [value_engine.q_hidden_buffer(batch) for _ in range(2)] if value_engine is not None else None
         self._qh_ws = value_engine.q_hidden_ws(batch) if value_engine is not None else None
@@ -215,6 +227,10 @@ class WordleRolloutEngine:
         self.sample_step = 0
 
     def close(self):
+        for ses1 in (getattr(self, "ses1", None), getattr(self, "vses1", None)):
+            if ses1 is not None and getattr(ses1, "_pinned", 0):
+                ses1.unpin_prefix()
+        self.pin_header = False
         if getattr(self, "_tok", None):
             self._L.lmrl_wordle_tok_destroy(self._tok)
             self._tok = None
@@ -225,6 +241,14 @@ class WordleRolloutEngine:
 
     def _ck(self, rc, what):
         _lib.check(rc, what)
+
+    def _fused_tail_ok(self, top_k: int, top_p: float, jax_stream: bool) -> bool:
+        """Where one launch can stand for sample_reduce + tok_accept + the next forward's embedding: policy-only Philox / greedy sampling without
+        warpers on the bf16 engine, single-token forwards on the LN-folded path that are neither ragged nor skinny (the library refuses the
+        rest, it never falls back)."""
+        from .gpt2 import KVSession
+        return (self.fused_tail and isinstance(self.ses, KVSession) and self.vses is None and not jax_stream and top_k <= 0 and top_p <= 0.0 and
+                bool(self._L.lmrl_gpt2_forward_takes_pre_embedded(self.eng._h, self.B, self.session_flags)))
 
     def run_episode(self, seeds: np.ndarray, temperature: float = 1.0, top_k: int = 0, sample_seed: int = 0,
                     scripted_guesses=None, steer_strength: float = 0.0, n_turns: int = W.N_TRIES, epoch=None, sampler: str = "philox", top_p: float = 0.0):
@@ -308,8 +332,9 @@ class WordleRolloutEngine:
         self._ck(L.lmrl_wordle_tok_begin(self._tok, tr, _lib.ptr(self.chunk_tok), _lib.ptr(self.chunk_cnt), B, sp), "tok_begin")
         def header(ses, ses1):
             if self.share_header:
-                ses1.reset()
-                ses1.forward(self.chunk_tok[:8], self.chunk_cnt[:1], 8)      # env 0's header chunk = everybody's header chunk
+                if not self.pin_header:     # else ses1 holds the header as a pinned prefix of the engine: nothing to compute here
+                    ses1.reset()
+                    ses1.forward(self.chunk_tok[:8], self.chunk_cnt[:1], 8)      # env 0's header chunk = everybody's header chunk
                 ses.broadcast_prefix_from(ses1, len(self.tokens.header))
             else:
                 ses.forward(self.chunk_tok, self.chunk_cnt, 8)
@@ -325,6 +350,7 @@ class WordleRolloutEngine:
                 self._warp_logits = torch.empty(B, self.eng.cfg.vocab_padded, dtype=torch.float32, device=self.dev)
             logits_out = self._warp_logits
         steered = scripted_guesses is not None and steer_strength != 0.0
+        fuse = self._fused_tail_ok(top_k, top_p, pol_key is not None)
         for turn in range(n_turns):
             tok_keys = None
             if pol_key is not None:
@@ -347,12 +373,23 @@ class WordleRolloutEngine:
                         if head is not None:
                             self.veng.q_hidden(head, self.vses.last_hidden, self.qh[i], self._qh_ws)
                             qops[i] = (self.qh[i], head.get("w2_x3", head["w2"]), head["b2"])
+                more = k < self.max_new - 1
                 self.ses.sample(p, steer_tok=steer, active=self.traj["gen_active"], logits_out=logits_out, q1=qops[0], q2=qops[1],
-                                want_logprob=False)
-                self._ck(L.lmrl_wordle_tok_accept(self._tok, tr, _lib.ptr(self.ses.token), k, _lib.ptr(self.next_tok),
-                                                  _lib.ptr(self.next_cnt), None, B, sp), "tok_accept")
-                if k < self.max_new - 1:
-                    both(lambda ses, _: ses.forward(self.next_tok, self.next_cnt, 1))
+                                want_logprob=False, **({"keep_partials": True} if fuse else {}))      # (a bf16 `KVSession` switch: `_fused_tail_ok`)
+                if fuse:    # merge + accept (+ the next forward's row embeddings, straight into its workspace) in one launch
+                    e, ses = self.eng, self.ses
+                    self._ck(L.lmrl_wordle_sample_accept_embed(self._tok, tr, _lib.ptr(ses.sample_ws), e.cfg.vocab_padded, self.tokens.pad,
+                                                               _lib.ptr(self.traj["gen_active"]), _lib.ptr(ses.token), None, k, _lib.ptr(self.next_tok),
+                                                               _lib.ptr(self.next_cnt), None, e._h if more else None, _lib.ptr(ses.ws[1]) if more else None,
+                                                               _lib.ptr(ses.len) if more else None, B, sp), "sample_accept_embed")
+                else:
+                    self._ck(L.lmrl_wordle_tok_accept(self._tok, tr, _lib.ptr(self.ses.token), k, _lib.ptr(self.next_tok),
+                                                      _lib.ptr(self.next_cnt), None, B, sp), "tok_accept")
+                if more:
+                    if fuse:
+                        self.ses.forward(self.next_tok, self.next_cnt, 1, pre_embedded=True)
+                    else:
+                        both(lambda ses, _: ses.forward(self.next_tok, self.next_cnt, 1))
                     yield
             self._ck(L.lmrl_wordle_tok_guess(self._tok, tr, _lib.ptr(self.guess), _lib.ptr(self.active), B, sp), "tok_guess")
             self.env.step_device(self.guess, self.active)
@@ -371,8 +408,9 @@ class WordleRolloutEngine:
 
     # ---- the online-RL hand-over: the finished episode as PPO data, on the device -------------------------------------
     def load_params(self, params) -> None:
-        """The trainer's fp32 parameters into the policy engine IN PLACE (`GPT2Engine.load_params`): captured episodes stay valid (they read the same
-        weight buffers; the shared header's K/V are recomputed at every episode start)."""
+        """The trainer's fp32 parameters into the policy engine IN PLACE (`GPT2Engine.load_params`): captured episodes stay valid — they read the same
+        weight buffers, and the shared header's K/V rows they broadcast are a pinned prefix that the engine prefills again inside this call
+        (without `pin_header`: recomputed at every episode start)."""
         self.eng.load_params(params)
 
     def ppo_records(self, n: Optional[int] = None):

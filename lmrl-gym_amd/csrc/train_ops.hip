@@ -644,9 +644,11 @@ __global__ __launch_bounds__(256) void lse_gather_kernel(const float *__restrict
     float mx = -INFINITY, s = 0.f;
     const int head = (int)((16 - (reinterpret_cast<uintptr_t>(row) & 15)) & 15) >> 2;        // scalars before the first 16-byte boundary
     const int nvec = (V - (head < V ? head : V)) >> 2;
+    // Logits of -inf (a masked vocabulary entry in caller-supplied logits) are legal: while a thread has met nothing finite its maximum is -inf and
+    // its sum stays 0 — exp(-inf - -inf) is never formed.  A row of nothing but -inf gives lse = -inf, as jax.nn.logsumexp does.
     auto add = [&](float x) {
         if (x > mx) { s = s * __expf(mx - x) + 1.f; mx = x; }
-        else s += __expf(x - mx);
+        else if (mx != -INFINITY) s += __expf(x - mx);
     };
     for (int c = tid; c < head && c < V; c += 256) add(row[c]);
     const float4 *rv = reinterpret_cast<const float4 *>(row + head);
@@ -654,7 +656,7 @@ __global__ __launch_bounds__(256) void lse_gather_kernel(const float *__restrict
         const float4 x = rv[q];
         const float gm = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
         if (gm > mx) { s *= __expf(mx - gm); mx = gm; }
-        s += (__expf(x.x - mx) + __expf(x.y - mx)) + (__expf(x.z - mx) + __expf(x.w - mx));
+        if (mx != -INFINITY) s += (__expf(x.x - mx) + __expf(x.y - mx)) + (__expf(x.z - mx) + __expf(x.w - mx));
     }
     for (int c = head + 4 * nvec + tid; c < V; c += 256) add(row[c]);
     // merge (max, sum) pairs: wave shuffle, then the four waves through LDS

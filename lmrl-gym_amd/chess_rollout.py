@@ -22,8 +22,9 @@ import numpy as np
 
 from . import _lib
 from .envs import chess as C
-from .gpt2 import FWD_RAGGED_ALWAYS, GPT2Engine, SampleParams
+from .gpt2 import FWD_RAGGED_ALWAYS
 from .maze_rollout import _decode_one, maze_out_str_process, token_byte_table
+from .turn_loop import TurnLoopEngine, decode_generation, summarize
 
 FEN_BYTES, ACTION_BYTES = C.FEN_BYTES, C.ACTION_BYTES
 _FIELDS = ("fen", "gen", "gen_len", "action", "result", "reward", "done", "opp_san", "reply", "n_turns", "live", "ep_reward", "cur_fen", "cur_len", "prev_fen", "prev_len", "keep", "out_tok",
@@ -83,12 +84,12 @@ def chess_summary(interactions):
         episode_length.append(len(rewards))
         rs.append(sum(rewards))
         dones.append(interaction[-1].done)
-    summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
+    summ = summarize
     return dict(reward=summ(np.asarray(rs, dtype=np.float32)), done=summ(np.asarray(dones, dtype=np.float32)), victories=summ(victories),
                 percent_illegals=summ(percent_illegals), episode_length=summ(episode_length), length=summ(episode_length))
 
 
-class ChessRolloutEngine:
+class ChessRolloutEngine(TurnLoopEngine):
     """B lock-step chess episodes (`FenChessHistoryEnv`: the observation is the current position, `preprocess_state_og`) driven by a GPT-2 policy
     on one GPU; the public face mirrors `MazeRolloutEngine`.
 
@@ -152,12 +153,8 @@ class ChessRolloutEngine:
         self._ctraj = _CTraj(*[self.traj[n].data_ptr() for n in _FIELDS])
         self.pos = z(B * self._L.lmrl_chess_pos_bytes(), dt=u8)
         self.fens_d, self.ok = z(B, FEN_BYTES, dt=u8), z(B, dt=u8)
-        self.chunk_tok, self.chunk_cnt = z(B * 16, dt=i32), z(B, dt=i32)
-        self.next_tok, self.next_cnt = z(B, dt=i32), z(B, dt=i32)
-        self.epoch = z(1, dt=i32)            # 4th Philox counter word of the sampler AND of the reply stream: (episode << 12) + turn, advanced on the device
+        self._alloc_turn_loop()              # (`epoch` is the 4th counter word of the reply stream too)
         self.turn_graph = None
-        self.episodes = 0
-        self._script = None                  # (steer ids [T + slack][max_new][B], turn counter [1], this turn's rows [max_new][B], strength)
         self._replies = None                 # int32 [T][B] injected reply indices
         self._starts: List[str] = [self.start] * B
         self._moves: List[List[str]] = [[] for _ in range(B)]
@@ -173,22 +170,12 @@ class ChessRolloutEngine:
         turn t the sampler of env b is steered (+`strength` on one logit per generated position; every logit is still computed and sampled) towards
         spelling that string the way the chess data spells moves (`preprocess_move`: blanks between the characters, a newline; `spaced=False`: the
         bare string and a newline), cut to max_new_tokens ids.  None switches it off.  Captured turn graphs are dropped."""
-        import torch
-        t = torch
         self.turn_graph = None
-        if san_strings is None:
-            self._script = None
-            return
-        assert len(san_strings) == self.T and all(len(r) == self.B for r in san_strings)
-        steer = np.full((self.T + 4 * self.T + 8, self.max_new, self.B), -1, dtype=np.int32)    # (slack: capture warm-ups advance the counter too)
-        for ti, row in enumerate(san_strings):
-            for b, s in enumerate(row):
-                if s is None:
-                    continue
-                ids = list(self.tok.encode(C.preprocess_move(s) if spaced else s + "\n"))[: self.max_new]
-                steer[ti, : len(ids), b] = ids
-        self._script = (t.from_numpy(steer).to(self.dev), t.zeros(1, dtype=t.int32, device=self.dev),
-                        t.full((self.max_new, self.B), -1, dtype=t.int32, device=self.dev), float(strength))
+        if san_strings is not None:
+            assert len(san_strings) == self.T and all(len(r) == self.B for r in san_strings)
+            spell = lambda s: None if s is None else self.tok.encode(C.preprocess_move(s) if spaced else s + "\n")
+            san_strings = [[spell(s) for s in row] for row in san_strings]
+        self._set_script(san_strings, strength)
 
     def set_scripted_replies(self, idx) -> None:
         """Device opponent: in turn t game b is answered with legal move `idx[t][b] mod count` in `lmrl_chess_describe`'s order instead of a drawn
@@ -209,16 +196,8 @@ class ChessRolloutEngine:
         self.ses = engine.session(self.B, self.ses.tmax, flags=self.ses.flags)
         self.turn_graph = None
 
-    def load_params(self, params) -> None:
-        """The trainer's fp32 parameters into the policy engine IN PLACE (`GPT2Engine.load_params`: a captured turn stays valid).  bf16 policy engines
-        only: a `GPT2EngineF32` policy is rebuilt from the trained weights and handed to `set_params`."""
-        if not isinstance(self.eng, GPT2Engine):
-            raise _lib.LmrlError(f"ChessRolloutEngine.load_params: in-place loading needs a bf16 GPT2Engine policy, not a {type(self.eng).__name__} "
-                                 "(build an engine from the new weights and call set_params)")
-        self.eng.load_params(params)
-
     # ---- one lock-step turn ------------------------------------------------------------------------------------------------------------
-    def _generate(self, temperature: float, top_k: int, sample_seed: int, logits_out=None):
+    def _agent_half(self, temperature: float, top_k: int, sample_seed: int, logits_out=None):
         """The kept prompt prefix, the prompt chunks behind it, the decode steps, ids -> SAN -> the agent's half-step."""
         L, sp, tr, B = self._L, _lib.stream_ptr(), ctypes.byref(self._ctraj), self.B
         ck = _lib.check
@@ -228,29 +207,20 @@ class ChessRolloutEngine:
             ck(L.lmrl_chess_tok_prompt(self._tok, tr, j, 16, self._max_input_length, self.n_chunks, _lib.ptr(self.chunk_tok), _lib.ptr(self.chunk_cnt), B, sp),
                "lmrl_chess_tok_prompt")
             self.ses.forward(self.chunk_tok, self.chunk_cnt, 16, len_bound_after=self.n_chunks * 16)
-        script = self._script
-        if script is not None:      # this turn's steer rows: row `turn counter` of the scripted table (a device-side index: the same launch in every replay)
-            ck(L.lmrl_gather_rows_bytes(script[0].data_ptr(), script[1].data_ptr(), script[2].data_ptr(), 1, self.max_new * B * 4, sp), "lmrl_gather_rows_bytes")
-        for k in range(self.max_new):
-            p = SampleParams(temperature, top_k, sample_seed, k, script[3] if script is not None else 0.0, 0.0, self.pad, _lib.ptr(self.epoch))
-            self.ses.sample(p, steer_tok=script[2][k] if script is not None else None, active=self.traj["gen_active"], logits_out=logits_out, want_logprob=False)
-            ck(L.lmrl_gen_accept(_lib.ptr(self.ses.token), _lib.ptr(self.traj["gen_active"]), _lib.ptr(self.traj["out_tok"]), _lib.ptr(self.traj["out_len"]),
-                                 _lib.ptr(self.next_tok), _lib.ptr(self.next_cnt), -1 if self.eos is None else int(self.eos), self.max_new, B, sp), "lmrl_gen_accept")
-            if k < self.max_new - 1:
-                self.ses.forward(self.next_tok, self.next_cnt, 1)
+        g = self.traj
+        self._generate(self.ses, (self.ses,), temperature, top_k, 0.0, sample_seed, 0.0, _lib.ptr(self.epoch), g["gen_active"], g["out_tok"], g["out_len"],
+                       self.next_tok, self.next_cnt, -1 if self.eos is None else int(self.eos), self.max_new, self._steer_rows(), logits_out)
         ck(L.lmrl_chess_tok_action(self._tok, tr, _lib.ptr(self.pos), B, sp), "lmrl_chess_tok_action")
 
     def _finish(self):
         L, sp, tr = self._L, _lib.stream_ptr(), ctypes.byref(self._ctraj)
         _lib.check(L.lmrl_chess_tok_result(self._tok, tr, _lib.ptr(self.pos), self.max_moves, self.B, sp), "lmrl_chess_tok_result")
-        self.epoch.add_(1)
-        if self._script is not None:
-            self._script[1].add_(1)
+        self._end_turn(self._script)
 
     def _turn(self, temperature: float, top_k: int, sample_seed: int, logits_out=None):
         """Device opponent: the whole turn, no host round trip (graph-capturable)."""
         L, sp, tr = self._L, _lib.stream_ptr(), ctypes.byref(self._ctraj)
-        self._generate(temperature, top_k, sample_seed, logits_out)
+        self._agent_half(temperature, top_k, sample_seed, logits_out)
         rp = self._replies
         _lib.check(L.lmrl_chess_tok_opponent(self._tok, tr, _lib.ptr(self.pos), int(sample_seed) & (2 ** 64 - 1), _lib.ptr(self.epoch), _lib.ptr(rp),
                                              int(rp.shape[0]) if rp is not None else 0, self.B, sp), "lmrl_chess_tok_opponent")
@@ -260,7 +230,7 @@ class ChessRolloutEngine:
         """Host engine pool: two halves around one hand-off — the agents' moves [B][8] down, the replies [B][8] up."""
         import torch
         L, sp, tr = self._L, _lib.stream_ptr(), ctypes.byref(self._ctraj)
-        self._generate(temperature, top_k, sample_seed, logits_out)
+        self._agent_half(temperature, top_k, sample_seed, logits_out)
         played = C.VectorChessBoards._unpack(self.traj["uci"].view(-1), 8)
         idx = [b for b, mv in enumerate(played) if mv]
         if idx:
@@ -282,20 +252,18 @@ class ChessRolloutEngine:
 
     def capture_turn(self, temperature: float = 1.0, top_k: int = 0, sample_seed: int = 0):
         """One turn (device opponent) as a hipGraph; `run_episode(..., use_graph=True)` replays it per turn."""
-        import torch
-        t = torch
         if self.opponent != "device":
             raise _lib.LmrlError("ChessRolloutEngine.capture_turn: a turn with a host engine pool has a host hand-off in the middle — it runs eagerly")
-        self._graph_args = (temperature, top_k, sample_seed)
-        self._logits = t.empty(self.B, self.eng.cfg.vocab_padded, dtype=t.float32, device=self.dev) if top_k > 0 else None
+        self._begin_capture(temperature, top_k, 0.0, sample_seed)
         self._begin([self.start] * self.B)
-        self._turn(temperature, top_k, sample_seed, self._logits)           # eager warm-up
-        t.cuda.synchronize()
-        g = t.cuda.CUDAGraph()
-        with t.cuda.graph(g, capture_error_mode="thread_local"):
-            self._turn(temperature, top_k, sample_seed, self._logits)
-        self.turn_graph = g
-        return g
+        self.turn_graph = self._capture(temperature, top_k, sample_seed, self._logits)
+        return self.turn_graph
+
+    def _graphs(self):
+        return self.turn_graph
+
+    def _recapture(self, temperature, top_k, top_p, sample_seed):
+        self.capture_turn(temperature, top_k, sample_seed)
 
     def _begin(self, starts: List[str], n_live: Optional[int] = None):
         import torch
@@ -312,14 +280,7 @@ class ChessRolloutEngine:
         self._starts, self._moves = list(starts), [[] for _ in range(self.B)]
 
     def _episode_begin(self, seeds, options, temperature, top_k, sample_seed, episode, use_graph, n_live=None):
-        import torch
-        t = torch
-        if use_graph:
-            if self.turn_graph is None or self._graph_args != (temperature, top_k, sample_seed):
-                self.capture_turn(temperature, top_k, sample_seed)
-            logits = self._logits
-        else:
-            logits = t.empty(self.B, self.eng.cfg.vocab_padded, dtype=t.float32, device=self.dev) if top_k > 0 else None
+        logits = self._episode_logits(use_graph, temperature, top_k, 0.0, sample_seed)
         assert len(seeds) == self.B
         if options is not None and not isinstance(options, (list, tuple)):
             options = [options] * self.B
@@ -328,9 +289,7 @@ class ChessRolloutEngine:
         bad = np.nonzero(self.ok.cpu().numpy() == 0)[0]
         if len(bad):
             raise ValueError(f"invalid FEN: {starts[int(bad[0])]!r}")
-        self.epoch.fill_(int(episode) << 12)
-        if self._script is not None:
-            self._script[1].zero_()
+        self._start_episode_counters(episode)
         if use_graph:
             return self.turn_graph.replay
         fn = self._turn if self.opponent == "device" else self._turn_host
@@ -344,12 +303,7 @@ class ChessRolloutEngine:
         if use_graph and self.opponent != "device":
             raise _lib.LmrlError("ChessRolloutEngine: use_graph needs the device opponent")
         turn = self._episode_begin(seeds, options, temperature, top_k, sample_seed, episode, use_graph, n_live)
-        n = self.T if max_turns is None else min(self.T, max_turns)
-        for i in range(n):
-            if sync_every and i and i % sync_every == 0 and not bool(self.traj["live"].any().item()):
-                break
-            turn()
-        return self.traj
+        return self._run_turns(lambda i: turn(), sync_every, max_turns)
 
     # ---- host views --------------------------------------------------------------------------------------------------------------------
     def _check_flags(self):
@@ -375,18 +329,6 @@ class ChessRolloutEngine:
                             ep_reward=float(h["ep_reward"][b])))
         return out
 
-    def _decode(self, ids: List[int]) -> str:
-        if self.eos is not None and self.eos in ids:
-            ids = ids[: ids.index(self.eos) + 1]
-        try:
-            return self.tok.decode(ids, skip_special_tokens=True)
-        except TypeError:
-            special = getattr(self.tok, "all_special_ids", None)
-            if special is None:
-                special = [t for t in (getattr(self.tok, "pad_token_id", None),) if t is not None]
-            special = set(special)
-            return self.tok.decode([i for i in ids if i not in special])
-
     def interactions(self, n: Optional[int] = None):
         """The finished episodes (of the first `n` games) as `List[List[InteractionTransition]]` — what `interact_environment` returns for the same
         rollouts (LLM_RL/environment.py:154-207 on FenChessHistoryEnv)."""
@@ -396,7 +338,7 @@ class ChessRolloutEngine:
             obs = [(Text(C.preprocess_state_og(f), False),) for f in rec["fen"] + [rec["final_fen"]]]
             trans = []
             for i in range(len(rec["fen"])):
-                act = Text(maze_out_str_process(self._decode(rec["gen"][i])), True)
+                act = Text(maze_out_str_process(decode_generation(self.tok, rec["gen"][i], self.eos)), True)
                 trans.append(InteractionTransition(obs[i], obs[i] + (act,), obs[i + 1], float(rec["reward"][i]), bool(rec["done"][i])))
             out.append(trans)
         return out
@@ -409,20 +351,8 @@ class ChessRolloutEngine:
         calls.  `use_graph` defaults to the device opponent's graph path."""
         if use_graph is None:
             use_graph = self.opponent == "device"
-        inter = []
-        launched = 0
-        while launched < n_rollouts:
-            actual = min(n_rollouts - launched, self.B)
-            seeds = [0] * self.B
-            seeds[:actual] = [next(seed_generator) for _ in range(actual)] if seed_generator is not None else [0] * actual
-            self.run_episode(seeds, env_options, temperature=temperature, top_k=top_k, sample_seed=sample_seed, episode=self.episodes, use_graph=use_graph,
-                             sync_every=sync_every, n_live=actual)
-            self.episodes += 1
-            launched += actual
-            for ep in self.interactions(actual):
-                inter.append(ep)
-                if interaction_callback is not None:
-                    interaction_callback(ep)
+        inter = self._eval_round(n_rollouts, seed_generator, env_options, interaction_callback,
+                                 dict(temperature=temperature, top_k=top_k, sample_seed=sample_seed, use_graph=use_graph, sync_every=sync_every))
         return inter, chess_summary(inter)
 
     # ---- the online-RL hand-over -------------------------------------------------------------------------------------------------------
@@ -454,12 +384,6 @@ class ChessRolloutEngine:
                    "lmrl_chess_tok_ppo_records")
         return PPORecords(tokens, ia, rw, n_tok, done, chain, pos, last, n_chains=B, chain_len_bound=max(int(total.cpu().numpy().max()), 1))
 
-    def ppo_data(self, inference, *, gamma: float, lam: float, kl_weight: float, max_length: Optional[int] = None, n: Optional[int] = None, **kw):
-        """`ppo_dataset_loader` of the online script on the episodes this engine just ran -> (DevicePPODataset, all_kls): see
-        `algorithms.ppo_device.ppo_data_from_records`."""
-        from .algorithms.ppo_device import ppo_data_from_records
-        return ppo_data_from_records(inference, self.ppo_records(n), gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, **kw)
-
     def ppo_rollouts(self, inference, n_rollouts: int, seed_generator=None, env_options=None, *, gamma: float, lam: float, kl_weight: float,
                      max_length: Optional[int] = None, use_advantage_whitening: bool = True, temperature: float = 1.0, top_k: int = 0, sample_seed: int = 0,
                      use_graph: Optional[bool] = None, **kw):
@@ -467,33 +391,20 @@ class ChessRolloutEngine:
         (DevicePPODataset over all transitions of all rollouts, all_kls, summary).  Per episode batch: the lock-step episode, then its PPO data while
         the record is in the engine's buffers; advantages whitened once over the action tokens of the whole round; `summary` has `text_env_eval`'s
         fields (from the record's rewards; no text is built)."""
-        import torch
-        from .algorithms.ppo_device import DevicePPODataset
-        from . import dist as D
         if use_graph is None:
             use_graph = self.opponent == "device"
-        parts, kls, stats = [], [], []
-        launched = 0
-        while launched < n_rollouts:
-            actual = min(n_rollouts - launched, self.B)
-            seeds = [0] * self.B
-            seeds[:actual] = [next(seed_generator) for _ in range(actual)] if seed_generator is not None else [0] * actual
-            self.run_episode(seeds, env_options, temperature=temperature, top_k=top_k, sample_seed=sample_seed, episode=self.episodes, use_graph=use_graph,
-                             n_live=actual)
-            self.episodes += 1
-            launched += actual
-            ds, kl = self.ppo_data(inference, gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, n=actual, use_advantage_whitening=False, **kw)
-            parts.append(ds); kls.append(kl)
-            rw = self.traj["reward"][:actual].cpu().numpy(); dn = self.traj["done"][:actual].cpu().numpy(); nt = self.traj["n_turns"][:actual].cpu().numpy()
-            for b in range(actual):
-                r = rw[b, : nt[b]]
-                stats.append((float(r.sum()), float(dn[b, max(nt[b] - 1, 0)]), float(1 in r), float((r[:-1] == -1).sum()) / max(len(r), 1) * 100, int(nt[b])))
-        ds = DevicePPODataset.concat(parts)
-        if use_advantage_whitening:
-            adv = ds.old_advantages
-            ds.old_advantages = D.whiten_distributed(adv.view(-1), ds.should_take_action.view(-1), shift_mean=True).view(adv.shape)
-        st = np.asarray(stats, dtype=np.float64).T
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
-        return ds, (kls[0] if len(kls) == 1 else torch.cat(kls)), dict(reward=summ(st[0].astype(np.float32)), done=summ(st[1].astype(np.float32)),
-                                                                       victories=summ(st[2]), percent_illegals=summ(st[3]),
-                                                                       episode_length=summ(st[4].astype(np.int64)), length=summ(st[4].astype(np.int64)))
+        return self._ppo_round(inference, n_rollouts, seed_generator, env_options, use_advantage_whitening,
+                               dict(temperature=temperature, top_k=top_k, sample_seed=sample_seed, use_graph=use_graph),
+                               dict(gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, **kw))
+
+    _DRAW_SEEDS = False          # the chess env's reset ignores its seeds
+    _SUMMARY = (("reward", 0, np.float32), ("done", 1, np.float32), ("victories", 2, np.float64), ("percent_illegals", 3, np.float64),
+                ("episode_length", 4, np.int64), ("length", 4, np.int64))
+
+    def _round_stats(self, actual: int):
+        rw = self.traj["reward"][:actual].cpu().numpy(); dn = self.traj["done"][:actual].cpu().numpy(); nt = self.traj["n_turns"][:actual].cpu().numpy()
+        stats = []
+        for b in range(actual):
+            r = rw[b, : nt[b]]
+            stats.append((float(r.sum()), float(dn[b, max(nt[b] - 1, 0)]), float(1 in r), float((r[:-1] == -1).sum()) / max(len(r), 1) * 100, int(nt[b])))
+        return np.asarray(stats, dtype=np.float64).T

@@ -26,7 +26,8 @@ import numpy as np
 
 from . import _lib
 from .envs import maze as M
-from .gpt2 import FWD_RAGGED_ALWAYS, FWD_SKINNY, GPT2Engine, SampleParams
+from .gpt2 import FWD_RAGGED_ALWAYS, FWD_SKINNY, GPT2Engine
+from .turn_loop import TurnLoopEngine, decode_generation, round_seeds, summarize
 
 _TOK_BYTES = 16
 
@@ -42,13 +43,7 @@ def maze_out_str_process(x: str) -> str:
 
 
 def _decode_one(tokenizer, i: int) -> str:
-    try:
-        return tokenizer.decode([i], skip_special_tokens=True)
-    except TypeError:
-        special = getattr(tokenizer, "all_special_ids", None)
-        if special is None:
-            special = [t for t in (getattr(tokenizer, "pad_token_id", None),) if t is not None]
-        return "" if i in special else tokenizer.decode([i])
+    return decode_generation(tokenizer, [i])
 
 
 def token_byte_table(tokenizer, vocab: int):
@@ -74,7 +69,7 @@ class _CHist(ctypes.Structure):            # lmrl_maze_hist (include/lmrl_amd.h)
                [("hcap", ctypes.c_int32), ("max_items", ctypes.c_int32)]
 
 
-class MazeRolloutEngine:
+class MazeRolloutEngine(TurnLoopEngine):
     """B lock-step Maze episodes driven by a GPT-2 policy on one GPU.
 
     env.last_k == 1 (the fully observed scripts): the prompt is a function of (goal, cell) — prompt table + prefix cache, below.
@@ -183,12 +178,9 @@ class MazeRolloutEngine:
                          ep_reward=z(B, dt=t.float32), obs_idx=z(B, dt=t.int32), out_tok=z(B, G, dt=t.int32), out_len=z(B, dt=t.int32),
                          gen_active=z(B, dt=t.uint8), act=z(B, dt=t.uint8), stepping=z(B, dt=t.uint8))
         self._ctraj = _CTraj(*[self.traj[n].data_ptr() for n, _ in _CTraj._fields_])
-        self.chunk_tok, self.chunk_cnt = z(B * 16, dt=t.int32), z(B, dt=t.int32)
-        self.next_tok, self.next_cnt = z(B, dt=t.int32), z(B, dt=t.int32)
-        self.epoch = z(1, dt=t.int32)                  # 4th Philox counter word: episode base + turn (device side: graph replays advance it)
+        self._alloc_turn_loop()
         self.env._alloc(batch)
         self.turn_graph = None
-        self.episodes = 0                              # episode batches run by text_env_eval so far: successive calls draw fresh sampler noise
         if prefix_cache:
             self.refresh_prefix_cache()
         # the tokenizer's encoding of the four action strings: what a legal action is in later prompts (last_k > 1: the next prompt is
@@ -228,29 +220,18 @@ class MazeRolloutEngine:
         self.env.close()
         self._drop_lanes()
 
-    _script = None      # (steer ids int32 [T][max_new][B], turn counter int32 [1], this turn's rows [max_new][B], strength)
-
     def set_scripted_actions(self, codes, strength: float = 30.0) -> None:
         """Synthetic-workload hook (bench.py / tools, as `WordleRolloutEngine`'s scripted guesses): `codes` int [T][B] of LMRL_MAZE_LEFT..DOWN — in
         turn t the sampler of env b is steered (+`strength` on one logit per generated position; every logit is still computed and sampled) towards
         spelling that move's text with the tokenizer's own ids, so that a random-init policy walks and its history window fills as a trained
         policy's does.  None switches it off.  Captured turn graphs are dropped (the steer operand becomes part of a turn)."""
-        import torch
-        t = torch
         self.turn_graph = None
-        if codes is None:
-            self._script = None
-            return
-        codes = np.asarray(codes, dtype=np.int64)
-        assert codes.shape == (self.T, self.B) and codes.min() >= 0 and codes.max() < 4
-        acts = [list(self.tok.encode(self.in_str_process(a))) for a in ("move left\n", "move right\n", "move up\n", "move down\n")]
-        table = np.full((4, self.max_new), -1, dtype=np.int32)
-        for i, a in enumerate(acts):
-            table[i, :min(len(a), self.max_new)] = a[:self.max_new]
-        steer = np.full((self.T + 4 * self.T + 8, self.max_new, self.B), -1, dtype=np.int32)   # [T (+ slack: capture warm-ups advance the counter too)][max_new][B]
-        steer[:self.T] = table[codes].transpose(0, 2, 1)
-        self._script = (t.from_numpy(steer).to(self.dev), t.zeros(1, dtype=t.int32, device=self.dev),
-                        t.full((self.max_new, self.B), -1, dtype=t.int32, device=self.dev), float(strength))
+        if codes is not None:
+            codes = np.asarray(codes, dtype=np.int64)
+            assert codes.shape == (self.T, self.B) and codes.min() >= 0 and codes.max() < 4
+            acts = [list(self.tok.encode(self.in_str_process(a))) for a in ("move left\n", "move right\n", "move up\n", "move down\n")]
+            codes = [[acts[c] for c in row] for row in codes.tolist()]
+        self._set_script(codes, strength)
 
     def _drop_lanes(self):
         for twin, _ in (self._lanes or [])[1:]:
@@ -280,18 +261,11 @@ class MazeRolloutEngine:
         self.eng = self.engines[0] = engine
         self.sessions[0] = self.ses = engine.session(self.B, self.ses.tmax, flags=self.ses.flags)
         self.turn_graph = None
-        self._drop_lanes()          # twins hold the old weights' sessions / prefix caches: rebuilt on the next concurrent call
-        if self.prefix_cache:
-            self.refresh_prefix_cache()
+        self._after_weights()
 
-    def load_params(self, params) -> None:
-        """The trainer's fp32 parameters into the policy engine IN PLACE (`GPT2Engine.load_params`: captured turns stay valid, they read the same
-        weight buffers), then the observation prefix cache again — its K/V rows were computed by the old weights.  bf16 policy engines only: a
-        `GPT2EngineF32` policy is rebuilt from the trained weights and handed to `set_params`."""
-        if not isinstance(self.eng, GPT2Engine):
-            raise _lib.LmrlError(f"MazeRolloutEngine.load_params: in-place loading needs a bf16 GPT2Engine policy, not a {type(self.eng).__name__} "
-                                 "(build an engine from the new weights and call set_params)")
-        self.eng.load_params(params)
+    def _after_weights(self):
+        """Twins hold the old weights' sessions / prefix caches (rebuilt on the next concurrent call); the observation prefix cache's K/V rows
+        were computed by the old weights."""
         self._drop_lanes()
         if self.prefix_cache:
             self.refresh_prefix_cache()
@@ -332,25 +306,11 @@ class MazeRolloutEngine:
                 ck(L.lmrl_maze_tok_prompt(self._tok, tr, j, 16, _lib.ptr(self.chunk_tok), _lib.ptr(self.chunk_cnt), B, sp), "maze_tok_prompt")
                 for ses in self.sessions:
                     ses.forward(self.chunk_tok, self.chunk_cnt, 16)
-        script = self._script
-        if script is not None:      # this turn's steer rows: row `turn counter` of the scripted table (a device-side index: the same launch in every replay)
-            ck(L.lmrl_gather_rows_bytes(script[0].data_ptr(), script[1].data_ptr(), script[2].data_ptr(), 1, self.max_new * B * 4, sp), "lmrl_gather_rows_bytes")
-        for k in range(self.max_new):
-            p = SampleParams(temperature, top_k, sample_seed, k, script[3] if script is not None else 0.0, self.beta, self.pad, _lib.ptr(self.epoch))
-            qops = [None, None]
-            if self.vses is not None:     # Q heads on the value base's last hidden state: relu(dense1) here, dense2 inside the sampler
-                for i, head in enumerate((self.q1, self.q2)):
-                    if head is not None:
-                        self.veng.q_hidden(head, self.vses.last_hidden, self.qh[i], self._qh_ws)
-                        qops[i] = (self.qh[i], head.get("w2_x3", head["w2"]), head["b2"])
-            self.ses.sample(p, steer_tok=script[2][k] if script is not None else None, active=self.traj["gen_active"], logits_out=logits_out, q1=qops[0],
-                            q2=qops[1], want_logprob=False)
-            ck(L.lmrl_gen_accept(_lib.ptr(self.ses.token), _lib.ptr(self.traj["gen_active"]), _lib.ptr(self.traj["out_tok"]),
-                                 _lib.ptr(self.traj["out_len"]), _lib.ptr(self.next_tok), _lib.ptr(self.next_cnt),
-                                 -1 if self.eos is None else int(self.eos), self.max_new, B, sp), "lmrl_gen_accept")
-            if k < self.max_new - 1:
-                for ses in self.sessions:
-                    ses.forward(self.next_tok, self.next_cnt, 1)
+        script = self._steer_rows()
+        g = self.traj
+        self._generate(self.ses, self.sessions, temperature, top_k, 0.0, sample_seed, self.beta, _lib.ptr(self.epoch), g["gen_active"], g["out_tok"],
+                       g["out_len"], self.next_tok, self.next_cnt, -1 if self.eos is None else int(self.eos), self.max_new, script, logits_out,
+                       self._q_operands if self.vses is not None else None)
         ck(L.lmrl_maze_tok_action(self._tok, tr, B, sp), "maze_tok_action")
         if self.last_k != 1:
             ck(L.lmrl_maze_hist_action(self._tok, tr, ctypes.byref(self._chist), _lib.ptr(self.ses.len),
@@ -359,21 +319,21 @@ class MazeRolloutEngine:
         ck(L.lmrl_maze_step(e._ctx, _lib.ptr(e.state), _lib.ptr(self.traj["act"]), _lib.ptr(self.traj["stepping"]), _lib.ptr(e.reward),
                             _lib.ptr(e.done), _lib.ptr(e.kind), _lib.ptr(e.walls), B, sp), "lmrl_maze_step")
         ck(L.lmrl_maze_tok_result(self._tok, tr, _lib.ptr(e.reward), _lib.ptr(e.done), _lib.ptr(e.kind), B, sp), "maze_tok_result")
-        self.epoch.add_(1)
-        if script is not None:
-            script[1].add_(1)
+        self._end_turn(script)
 
-    def _reset_script_counter(self):
-        if self._script is not None:
-            self._script[1].zero_()
+    def _q_operands(self):
+        """Q heads on the value base's last hidden state: relu(dense1) here, dense2 inside the sampler."""
+        qops = [None, None]
+        for i, head in enumerate((self.q1, self.q2)):
+            if head is not None:
+                self.veng.q_hidden(head, self.vses.last_hidden, self.qh[i], self._qh_ws)
+                qops[i] = (self.qh[i], head.get("w2_x3", head["w2"]), head["b2"])
+        return qops
 
     def _capture_history_turns(self, temperature: float, top_k: int, sample_seed: int):
         """last_k > 1: one hipGraph per KIND of turn — the append turn (a fixed number of 16-token chunks) and one re-prefill turn per distinct
         chunk count of the schedule (the window's token bound grows until it reaches max_input_length)."""
-        import torch
-        t = torch
-        self._graph_args = (temperature, top_k, sample_seed)
-        self._logits = t.empty(self.B, self.eng.cfg.vocab_padded, dtype=t.float32, device=self.dev) if top_k > 0 else None
+        self._begin_capture(temperature, top_k, 0.0, sample_seed)
         self._turn_graphs = {}
         kinds = {}
         for ti in range(self.T):
@@ -381,15 +341,11 @@ class MazeRolloutEngine:
             kinds.setdefault(key, ti)
         for key, ti in kinds.items():
             self.env.reset_device([0] * self.B)
-            self._reset_script_counter()
+            if self._script is not None:
+                self._script[1].zero_()
             self._hist_begin()
             _lib.check(self._L.lmrl_maze_tok_begin(self._tok, ctypes.byref(self._ctraj), self.B, _lib.stream_ptr()), "maze_tok_begin")
-            self._turn(temperature, top_k, sample_seed, self._logits, turn_index=ti)           # eager warm-up
-            t.cuda.synchronize()
-            g = t.cuda.CUDAGraph()
-            with t.cuda.graph(g, capture_error_mode="thread_local"):
-                self._turn(temperature, top_k, sample_seed, self._logits, turn_index=ti)
-            self._turn_graphs[key] = g
+            self._turn_graphs[key] = self._capture(temperature, top_k, sample_seed, self._logits, turn_index=ti)
         self.turn_graph = True
 
     def _hist_begin(self):
@@ -408,50 +364,34 @@ class MazeRolloutEngine:
 
     def capture_turn(self, temperature: float = 1.0, top_k: int = 0, sample_seed: int = 0):
         """One turn (~ max_new x n_layer x 7 launches) as a hipGraph; `run_episode(..., use_graph=True)` replays it per turn."""
-        import torch
-        t = torch
         if self.last_k != 1:
             return self._capture_history_turns(temperature, top_k, sample_seed)
-        self._graph_args = (temperature, top_k, sample_seed)
-        self._logits = t.empty(self.B, self.eng.cfg.vocab_padded, dtype=t.float32, device=self.dev) if top_k > 0 else None
+        self._begin_capture(temperature, top_k, 0.0, sample_seed)
         self.env.reset_device([0] * self.B)
         _lib.check(self._L.lmrl_maze_tok_begin(self._tok, ctypes.byref(self._ctraj), self.B, _lib.stream_ptr()), "maze_tok_begin")
-        self._turn(temperature, top_k, sample_seed, self._logits)           # eager warm-up
-        t.cuda.synchronize()
-        g = t.cuda.CUDAGraph()
-        with t.cuda.graph(g, capture_error_mode="thread_local"):
-            self._turn(temperature, top_k, sample_seed, self._logits)
-        self.turn_graph = g
-        return g
+        self.turn_graph = self._capture(temperature, top_k, sample_seed, self._logits)
+        return self.turn_graph
+
+    def _graphs(self):
+        return self.turn_graph
+
+    def _recapture(self, temperature, top_k, top_p, sample_seed):
+        self.capture_turn(temperature, top_k, sample_seed)
 
     def run_episode(self, seeds, options=None, temperature: float = 1.0, top_k: int = 0, sample_seed: int = 0, episode: int = 0,
                     use_graph: bool = False, sync_every: int = 8, max_turns: Optional[int] = None):
         """One full episode for all B envs; returns the device record dict (read after a sync).  The host peeks at the live flags every
         `sync_every` turns to stop early (0: never — fixed T turns, fully asynchronous)."""
         turn = self._episode_begin(seeds, options, temperature, top_k, sample_seed, episode, use_graph)
-        n = self.T if max_turns is None else min(self.T, max_turns)
-        for i in range(n):
-            if sync_every and i and i % sync_every == 0 and not bool(self.traj["live"].any().item()):
-                break
-            turn()
-        return self.traj
+        return self._run_turns(lambda i: turn(), sync_every, max_turns)
 
     def _episode_begin(self, seeds, options, temperature, top_k, sample_seed, episode, use_graph):
         """Reset + first bookkeeping of an episode on the CURRENT stream; returns the callable that enqueues one lock-step turn."""
-        import torch
-        t = torch
-        if use_graph:
-            if self.turn_graph is None or self._graph_args != (temperature, top_k, sample_seed):
-                self.capture_turn(temperature, top_k, sample_seed)
-            logits = self._logits
-        else:
-            logits = t.empty(self.B, self.eng.cfg.vocab_padded, dtype=t.float32, device=self.dev) if top_k > 0 else None
+        logits = self._episode_logits(use_graph, temperature, top_k, 0.0, sample_seed)
         assert len(seeds) == self.B
         self.env.reset_device(list(seeds), options)
         _lib.check(self._L.lmrl_maze_tok_begin(self._tok, ctypes.byref(self._ctraj), self.B, _lib.stream_ptr()), "maze_tok_begin")
-        self.epoch.fill_(int(episode) << 12)
-        if self._script is not None:
-            self._script[1].zero_()
+        self._start_episode_counters(episode)
         if self.last_k != 1:
             self._hist_begin()
 
@@ -583,12 +523,6 @@ class MazeRolloutEngine:
         call(cap, tokens, ia, rw)
         return PPORecords(tokens, ia, rw, n_tok, done, chain, pos, last, n_chains=B, chain_len_bound=max(int(total.cpu().numpy().max()), 1))
 
-    def ppo_data(self, inference, *, gamma: float, lam: float, kl_weight: float, max_length: Optional[int] = None, n: Optional[int] = None, **kw):
-        """`ppo_dataset_loader` of the Maze online script on the episodes this engine just ran -> (DevicePPODataset, all_kls): see
-        `algorithms.ppo_device.ppo_data_from_records`."""
-        from .algorithms.ppo_device import ppo_data_from_records
-        return ppo_data_from_records(inference, self.ppo_records(n), gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, **kw)
-
     def ppo_rollouts(self, inference, n_rollouts: int, seed_generator=None, env_options=None, *, gamma: float, lam: float, kl_weight: float,
                      max_length: Optional[int] = None, use_advantage_whitening: bool = True, temperature: float = 1.0, top_k: int = 0, sample_seed: int = 0,
                      use_graph: bool = True, **kw):
@@ -596,32 +530,18 @@ class MazeRolloutEngine:
         (maze/ppo/train_ppo_online.py:431-483) -> (DevicePPODataset over all transitions of all rollouts, all_kls, summary).  Per episode batch: the
         lock-step episode, then its PPO data while the record is in the engine's buffers; advantages whitened once over the action tokens of the whole
         round; `summary` has `text_env_eval`'s shape (from the per-env counters; no text is built)."""
-        import torch
-        from .algorithms.ppo_device import DevicePPODataset
-        from . import dist as D
-        parts, kls, stats = [], [], []
-        launched = 0
-        while launched < n_rollouts:
-            actual = min(n_rollouts - launched, self.B)
-            seeds = [0] * self.B
-            seeds[:actual] = [next(seed_generator) for _ in range(actual)] if seed_generator is not None else np.random.randint(0, 2 ** 31 - 1, size=actual).tolist()
-            self.run_episode(seeds, env_options, temperature=temperature, top_k=top_k, sample_seed=sample_seed, episode=self.episodes, use_graph=use_graph)
-            self.episodes += 1
-            launched += actual
-            ds, kl = self.ppo_data(inference, gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, n=actual, use_advantage_whitening=False, **kw)
-            parts.append(ds); kls.append(kl)
-            kind = self.traj["kind"][:actual].cpu().numpy(); nt = self.traj["n_turns"][:actual].cpu().numpy()
-            last_kind = kind[np.arange(actual), np.maximum(nt - 1, 0)]
-            stats.append(np.stack([self.traj["ep_reward"][:actual].cpu().numpy().astype(np.float64), ((last_kind == 1) | (last_kind == 2)).astype(np.float64),
-                                   nt.astype(np.float64)]))
-        ds = DevicePPODataset.concat(parts)
-        if use_advantage_whitening:
-            adv = ds.old_advantages
-            ds.old_advantages = D.whiten_distributed(adv.view(-1), ds.should_take_action.view(-1), shift_mean=True).view(adv.shape)
-        st = np.concatenate(stats, axis=1)
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
-        return ds, (kls[0] if len(kls) == 1 else torch.cat(kls)), dict(reward=summ(st[0].astype(np.float32)), done=summ(st[1].astype(np.float32)),
-                                                                       length=summ(st[2].astype(np.int64)))
+        return self._ppo_round(inference, n_rollouts, seed_generator, env_options, use_advantage_whitening,
+                               dict(temperature=temperature, top_k=top_k, sample_seed=sample_seed, use_graph=use_graph),
+                               dict(gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, **kw))
+
+    def _round_episode(self, seeds, env_options, actual, **run_kw):
+        return self.run_episode(seeds, env_options, episode=self.episodes, **run_kw)       # (idle envs of a partial batch play along: `n=actual` drops them)
+
+    def _round_stats(self, actual: int):
+        kind = self.traj["kind"][:actual].cpu().numpy(); nt = self.traj["n_turns"][:actual].cpu().numpy()
+        last_kind = kind[np.arange(actual), np.maximum(nt - 1, 0)]
+        return np.stack([self.traj["ep_reward"][:actual].cpu().numpy().astype(np.float64), ((last_kind == 1) | (last_kind == 2)).astype(np.float64),
+                         nt.astype(np.float64)])
 
     # ---- host views ----------------------------------------------------------------------------------------------------------------
     def records(self):
@@ -636,16 +556,6 @@ class MazeRolloutEngine:
             out.append(dict(pos=pos, gen=gen, action=h["action"][b, :n].copy(), reward=h["reward"][b, :n].copy(), kind=h["kind"][b, :n].copy(),
                             goal=(int(st[b, 2]), int(st[b, 3])), final_pos=(int(st[b, 0]), int(st[b, 1])), live=bool(h["live"][b])))
         return out
-
-    def _decode(self, ids: List[int]) -> str:
-        try:
-            return self.tok.decode(ids, skip_special_tokens=True)
-        except TypeError:
-            special = getattr(self.tok, "all_special_ids", None)
-            if special is None:
-                special = [t for t in (getattr(self.tok, "pad_token_id", None),) if t is not None]
-            special = set(special)
-            return self.tok.decode([i for i in ids if i not in special])
 
     def interactions(self):
         """The finished episodes as `List[List[InteractionTransition]]` — what `interact_environment` returns for the same rollouts
@@ -702,7 +612,7 @@ class MazeRolloutEngine:
         def action(ids):
             t = act_cache.get(ids)
             if t is None:
-                t = act_cache[ids] = Text(maze_out_str_process(self._decode(list(ids))), True)
+                t = act_cache[ids] = Text(maze_out_str_process(decode_generation(self.tok, list(ids))), True)
             return t
         pos, gen, gen_len, reward, kinds, n_turns = h["pos"], h["gen"], h["gen_len"], h["reward"], h["kind"], h["n_turns"]
         out = []
@@ -786,9 +696,7 @@ class MazeRolloutEngine:
                 if launched >= n_rollouts:
                     break
                 actual = min(n_rollouts - launched, self.B)
-                seeds = [0] * self.B
-                seeds[:actual] = [next(seed_generator) for _ in range(actual)] if seed_generator is not None else \
-                    np.random.randint(0, 2 ** 31 - 1, size=actual).tolist()
+                seeds = round_seeds(self.B, actual, seed_generator)
                 with torch.cuda.stream(st):
                     turn = eng._episode_begin(seeds, options, temperature, top_k, sample_seed, self.episodes, use_graph)
                 self.episodes += 1
@@ -817,5 +725,5 @@ class MazeRolloutEngine:
         absorb(pending)
         for _, st in lanes[1:]:
             main.wait_stream(st)
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
-        return inter, dict(reward=summ(np.asarray(rewards, dtype=np.float32)), done=summ(np.asarray(dones, dtype=np.float32)), length=summ(lengths))
+        return inter, dict(reward=summarize(np.asarray(rewards, dtype=np.float32)), done=summarize(np.asarray(dones, dtype=np.float32)),
+                           length=summarize(lengths))

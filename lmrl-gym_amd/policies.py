@@ -19,6 +19,7 @@ from . import _lib
 from .environment import BatchedTextPolicy, Text, TextHistory, text_history_to_str
 from . import jax_prng
 from .gpt2 import FWD_RAGGED_ALWAYS, RNG_JAX, GPT2Engine, SampleParams
+from .turn_loop import decode_generation
 
 
 class _Generator:
@@ -206,16 +207,7 @@ class GPT2PPOPolicy(BatchedTextPolicy):
         """The reference decodes generations with `batch_decode(..., skip_special_tokens=True)`
         (value_rl_base/base_interface.py:126, bc/core.py:102): special tokens (eos / pad) never reach the action Text.  An eos that
         is ordinary text (Wordle: eos = the '\n' token, train_ilql_gpt2.py:393) is not special and stays."""
-        try:
-            return self.tokenizer.decode(ids, skip_special_tokens=True)
-        except TypeError:
-            # minimal tokenizers without the keyword: drop what THEY declare special (`all_special_ids`; default: only the pad id —
-            # an eos id is ordinary text unless the tokenizer says otherwise, exactly as '\n' is for the GPT-2 tokenizer)
-            special = getattr(self.tokenizer, "all_special_ids", None)
-            if special is None:
-                special = [t for t in (getattr(self.tokenizer, "pad_token_id", None),) if t is not None]
-            special = set(special)
-            return self.tokenizer.decode([t for t in ids if t not in special])
+        return decode_generation(self.tokenizer, ids)
 
     def set_params(self, engine: GPT2Engine) -> None:
         """PPOPolicy.set_params (ppo/base_interface.py:821-823): swap in freshly trained weights."""

@@ -17,6 +17,7 @@ import numpy as np
 from . import _lib
 from .envs import wordle as W
 from .gpt2 import GPT2Engine, SampleParams
+from .turn_loop import finish_ppo_round, round_seeds, summarize
 
 def gpt2_byte_token_id(byte: int) -> int:
     """Id of the single-byte token of `byte` in GPT-2's byte-level BPE vocabulary, from the PUBLISHED construction (openai/gpt-2
@@ -447,21 +448,9 @@ class WordleRolloutEngine:
         the round (ppo/base_interface.py:609-615 whitens over every chain handed to the call), and `summary` has `text_env_eval`'s shape, from the
         per-env counters (no text is built)."""
         import torch
-        from .algorithms.ppo_device import DevicePPODataset
-        from . import dist as D
-        n_batches = -(-n_rollouts // self.B)
-        seeds_all = np.zeros((n_batches, self.B), dtype=np.uint64)
-        for k in range(n_batches):
-            n_k = min(n_rollouts - k * self.B, self.B)
-            seeds_all[k, :n_k] = [next(seed_generator) for _ in range(n_k)] if seed_generator is not None else np.random.randint(0, 2 ** 31 - 1, size=n_k)
         scripted = scripted_guesses_fn is not None
-        key = (float(temperature), int(sample_seed), float(steer_strength), scripted, int(top_k), float(top_p or 0.0))
-        want_graph = (getattr(self, "_eval_graph_key", None) == key or n_batches >= 4) if use_graph is None else bool(use_graph)
-        seeds_dev = torch.from_numpy(seeds_all.view(np.int64)).to(self.dev)
-        if want_graph and getattr(self, "_eval_graph_key", None) != key:
-            self.capture_episode(temperature=temperature, sample_seed=sample_seed, steer_strength=steer_strength, scripted=scripted, top_k=top_k,
-                                 top_p=top_p or 0.0)
-            self._eval_graph_key = key
+        n_batches, seeds_all, seeds_dev, want_graph = self._plan_round(n_rollouts, seed_generator, temperature, sample_seed, steer_strength, scripted, top_k,
+                                                                       top_p, use_graph)
         parts, kls, stats = [], [], []
         ev = lambda: (lambda e: (e.record(), e)[1])(torch.cuda.Event(enable_timing=True))
         t_roll = 0.0
@@ -483,17 +472,37 @@ class WordleRolloutEngine:
                 torch.cuda.synchronize()
                 t_roll += e0.elapsed_time(e1)
             parts.append(ds); kls.append(kl)
-            stats.append(np.stack([self.traj[name][:n_k].cpu().numpy().astype(np.float64) for name in ("ep_reward", "env_done", "n_steps")]))
-        ds = DevicePPODataset.concat(parts)
-        if use_advantage_whitening:
-            adv = ds.old_advantages
-            ds.old_advantages = D.whiten_distributed(adv.view(-1), ds.should_take_action.view(-1), shift_mean=True).view(adv.shape)
-        st = np.concatenate(stats, axis=1)
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
-        summary = dict(reward=summ(st[0].astype(np.float32)), done=summ(st[1].astype(np.float32)), length=summ(st[2].astype(np.int64)))
+            stats.append(self._round_stats(n_k))
+        ds, all_kls = finish_ppo_round(parts, kls, use_advantage_whitening)
         if timings is not None:
             timings["rollout_ms"] = timings.get("rollout_ms", 0.0) + t_roll
-        return ds, (kls[0] if len(kls) == 1 else torch.cat(kls)), summary
+        return ds, all_kls, self._round_summary(stats)
+
+    def _plan_round(self, n_rollouts, seed_generator, temperature, sample_seed, steer_strength, scripted, top_k, top_p, use_graph):
+        """The seeds of a round's ceil(n / B) episode batches (uint64 [n_batches][B], 0 for the idle envs of a partial last batch; on the device too
+        when the round replays the episode graph) and the eager / graph choice -> (n_batches, seeds, device seeds or None, want_graph); captures the
+        episode when the graph is wanted and the captured one has another key."""
+        import torch
+        n_batches = -(-n_rollouts // self.B)
+        seeds_all = np.zeros((n_batches, self.B), dtype=np.uint64)
+        for k in range(n_batches):
+            seeds_all[k] = round_seeds(self.B, min(n_rollouts - k * self.B, self.B), seed_generator)
+        key = (float(temperature), int(sample_seed), float(steer_strength), scripted, int(top_k), float(top_p or 0.0))
+        want_graph = (getattr(self, "_eval_graph_key", None) == key or n_batches >= 4) if use_graph is None else bool(use_graph)
+        seeds_dev = torch.from_numpy(seeds_all.view(np.int64)).to(self.dev) if want_graph else None
+        if want_graph and getattr(self, "_eval_graph_key", None) != key:
+            self.capture_episode(temperature=temperature, sample_seed=sample_seed, steer_strength=steer_strength, scripted=scripted, top_k=top_k,
+                                 top_p=top_p or 0.0)
+            self._eval_graph_key = key
+        return n_batches, seeds_all, seeds_dev, want_graph
+
+    def _round_stats(self, n_k: int):
+        return np.stack([self.traj[name][:n_k].cpu().numpy().astype(np.float64) for name in ("ep_reward", "env_done", "n_steps")])
+
+    @staticmethod
+    def _round_summary(stats):
+        st = np.concatenate(stats, axis=1)
+        return dict(reward=summarize(st[0].astype(np.float32)), done=summarize(st[1].astype(np.float32)), length=summarize(st[2].astype(np.int64)))
 
     def record_rollouts(self, n_rollouts: int, seed_generator=None, temperature: float = 1.0, sample_seed: int = 0, use_graph: Optional[bool] = None,
                         top_k: int = 0, top_p: float = 0.0):
@@ -503,18 +512,7 @@ class WordleRolloutEngine:
         the online filtered-BC loop feeds `offline_device.filter_records` / `mask_data_from_records`; no text, no host token data."""
         import torch
         from .algorithms.ppo_device import PPORecords
-        n_batches = -(-n_rollouts // self.B)
-        seeds_all = np.zeros((n_batches, self.B), dtype=np.uint64)
-        for k in range(n_batches):
-            n_k = min(n_rollouts - k * self.B, self.B)
-            seeds_all[k, :n_k] = [next(seed_generator) for _ in range(n_k)] if seed_generator is not None else np.random.randint(0, 2 ** 31 - 1, size=n_k)
-        key = (float(temperature), int(sample_seed), 0.0, False, int(top_k), float(top_p or 0.0))
-        want_graph = (getattr(self, "_eval_graph_key", None) == key or n_batches >= 4) if use_graph is None else bool(use_graph)
-        if want_graph:
-            seeds_dev = torch.from_numpy(seeds_all.view(np.int64)).to(self.dev)
-            if getattr(self, "_eval_graph_key", None) != key:
-                self.capture_episode(temperature=temperature, sample_seed=sample_seed, steer_strength=0.0, scripted=False, top_k=top_k, top_p=top_p or 0.0)
-                self._eval_graph_key = key
+        n_batches, seeds_all, seeds_dev, want_graph = self._plan_round(n_rollouts, seed_generator, temperature, sample_seed, 0.0, False, top_k, top_p, use_graph)
         parts, stats = [], []
         for k in range(n_batches):
             n_k = min(n_rollouts - k * self.B, self.B)
@@ -525,11 +523,9 @@ class WordleRolloutEngine:
                 self.episodes += 1
             r = self.ppo_records(n_k)
             parts.append([x.clone() for x in (r.tokens, r.is_action, r.reward, r.n_tok, r.done)])
-            stats.append(np.stack([self.traj[name][:n_k].cpu().numpy().astype(np.float64) for name in ("ep_reward", "env_done", "n_steps")]))
+            stats.append(self._round_stats(n_k))
         rec = PPORecords(*[torch.cat([p[i] for p in parts]).contiguous() for i in range(5)])
-        st = np.concatenate(stats, axis=1)
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
-        return rec, dict(reward=summ(st[0].astype(np.float32)), done=summ(st[1].astype(np.float32)), length=summ(st[2].astype(np.int64)))
+        return rec, self._round_summary(stats)
 
     # ---- the script-level call on the device engine -----------------------------------------------------------------
     def interactions(self, decode=None):
@@ -701,6 +697,6 @@ class WordleRolloutEngine:
             absorb(*pending.popleft())
         for _, st in lanes[1:]:
             main.wait_stream(st)
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
+        summ = summarize
         return inter, dict(reward=summ(np.asarray(rewards, dtype=np.float32)), done=summ(np.asarray(dones, dtype=np.float32)), length=summ(lengths))
 

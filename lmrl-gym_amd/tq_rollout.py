@@ -23,8 +23,9 @@ import numpy as np
 
 from . import _lib
 from .envs import twenty_questions as TQ
-from .gpt2 import FWD_RAGGED_ALWAYS, GPT2Engine, SampleParams
+from .gpt2 import FWD_RAGGED_ALWAYS
 from .maze_rollout import _decode_one, maze_out_str_process, token_byte_table
+from .turn_loop import TurnLoopEngine, decode_generation, summarize
 
 ORACLE_PREFIX = "Answer the question about the object truthfully.\nobject: {word}\nquestion: "
 ORACLE_SUFFIX = "\nanswer (yes or no): "
@@ -120,7 +121,7 @@ def _is_script_out_str_process(fn: Callable[[str], str]) -> bool:
         return False
 
 
-class TwentyQuestionsRolloutEngine:
+class TwentyQuestionsRolloutEngine(TurnLoopEngine):
     """B lock-step Twenty Questions episodes: `engine` asks, `oracle_engine` answers, on one GPU; the public face mirrors `ChessRolloutEngine`.
 
     `env`: a `TwentyQuestionsPolicyEnvironment` / `BatchedTwentyQuestionsPolicyEnvironment` — its `word_list` and `max_conversation_length` are
@@ -204,17 +205,12 @@ class TwentyQuestionsRolloutEngine:
                          feed_start=z(B, dt=i32), feed_len=z(B, dt=i32), o_prompt=z(B, self.pcap, dt=i32), o_len=z(B, dt=i32), o_prev=z(B, self.pcap, dt=i32),
                          o_prev_len=z(B, dt=i32), o_keep=z(B, dt=i32), flags=z(1, dt=i32))
         self._ctraj = _CTraj(*[self.traj[n].data_ptr() for n in _FIELDS], self.hist_bound, self.pcap)
-        self.chunk_tok, self.chunk_cnt = z(B * 16, dt=i32), z(B, dt=i32)
-        self.next_tok, self.next_cnt = z(B, dt=i32), z(B, dt=i32)
+        self._alloc_turn_loop()              # (`epoch`: of the guesser's sampler)
         self.o_next_tok, self.o_next_cnt = z(B, dt=i32), z(B, dt=i32)
         self.seeds_d, self.det_d, self.draws_d = z(B, dt=t.int64), z(B, dt=u8), z(B, dt=i32)
         self.mt = z(self._L.lmrl_mt_bytes(B), dt=u8)
         self.bound_d = t.tensor([len(self.word_list)], dtype=i32, device=self.dev)
-        self.epoch = z(1, dt=i32)            # 4th Philox counter word of the guesser's sampler: (episode << 12) + turn, advanced on the device
         self.turn_graphs = {}
-        self._graph_args = None
-        self.episodes = 0
-        self._script = None                  # (steer ids [T + slack][max_new][B], turn counter [1], this turn's rows [max_new][B], strength)
         self._answers = None                 # int8 [B][T'] injected answer codes
         self._final = True                   # the host's re-judgement of the flagged turns has been applied to the record
 
@@ -228,22 +224,11 @@ class TwentyQuestionsRolloutEngine:
         """Synthetic-workload hook (tools, tests; as `ChessRolloutEngine.set_scripted_actions`): `texts` [T][B] of str (None: no steering) — in turn
         t the guesser's sampler of env b is steered (+`strength` on one logit per generated position; every logit is still computed and sampled)
         towards spelling that text and a newline, cut to max_new_tokens ids.  None switches it off.  Captured turn graphs are dropped."""
-        import torch
-        t = torch
         self.turn_graphs = {}
-        if texts is None:
-            self._script = None
-            return
-        assert len(texts) == self.T and all(len(r) == self.B for r in texts)
-        steer = np.full((self.T + 4 * self.T + 8, self.max_new, self.B), -1, dtype=np.int32)    # (slack: capture warm-ups advance the counter too)
-        for ti, row in enumerate(texts):
-            for b, s in enumerate(row):
-                if s is None:
-                    continue
-                ids = list(self.tok.encode(s + "\n"))[: self.max_new]
-                steer[ti, : len(ids), b] = ids
-        self._script = (t.from_numpy(steer).to(self.dev), t.zeros(1, dtype=t.int32, device=self.dev),
-                        t.full((self.max_new, self.B), -1, dtype=t.int32, device=self.dev), float(strength))
+        if texts is not None:
+            assert len(texts) == self.T and all(len(r) == self.B for r in texts)
+            texts = [[None if s is None else self.tok.encode(s + "\n") for s in row] for row in texts]
+        self._set_script(texts, strength)
 
     def set_scripted_answers(self, codes) -> None:
         """The oracle's answer of env b in turn t becomes codes[b][t] (1 "Yes.", 0 "No.", < 0: ask the model; turns past the table repeat its last
@@ -266,13 +251,7 @@ class TwentyQuestionsRolloutEngine:
         self.ses = engine.session(self.B, self.ses.tmax, flags=self.ses.flags)
         self.turn_graphs = {}
 
-    def load_params(self, params) -> None:
-        """The trainer's fp32 parameters into the guesser engine IN PLACE (`GPT2Engine.load_params`: captured turns stay valid).  bf16 engines only: a
-        `GPT2EngineF32` guesser is rebuilt from the trained weights and handed to `set_params`."""
-        if not isinstance(self.eng, GPT2Engine):
-            raise _lib.LmrlError(f"TwentyQuestionsRolloutEngine.load_params: in-place loading needs a bf16 GPT2Engine guesser, not a {type(self.eng).__name__} "
-                                 "(build an engine from the new weights and call set_params)")
-        self.eng.load_params(params)
+    _POLICY = "guesser"
 
     # ---- one lock-step turn ------------------------------------------------------------------------------------------------------------
     def _feed_guesser(self, n_chunks: int):
@@ -289,36 +268,22 @@ class TwentyQuestionsRolloutEngine:
         # hist_bound + max_new and pcap + oracle_max_new positions; conversations or prompts that would not fit are refused there)
         for ses in (self.ses, self.oses):
             ses._len_bound = 0
-        script = self._script
-        if script is not None:      # this turn's steer rows: row `turn counter` of the scripted table (a device-side index: the same launch in every replay)
-            ck(L.lmrl_gather_rows_bytes(script[0].data_ptr(), script[1].data_ptr(), script[2].data_ptr(), 1, self.max_new * B * 4, sp), "lmrl_gather_rows_bytes")
-        eos = -1 if self.eos is None else int(self.eos)
-        for k in range(self.max_new):
-            p = SampleParams(temperature, top_k, sample_seed, k, script[3] if script is not None else 0.0, 0.0, self.pad, _lib.ptr(self.epoch), top_p)
-            self.ses.sample(p, steer_tok=script[2][k] if script is not None else None, active=self.traj["gen_active"], logits_out=logits_out, want_logprob=False)
-            ck(L.lmrl_gen_accept(_lib.ptr(self.ses.token), _lib.ptr(self.traj["gen_active"]), _lib.ptr(self.traj["out_tok"]), _lib.ptr(self.traj["out_len"]),
-                                 _lib.ptr(self.next_tok), _lib.ptr(self.next_cnt), eos, self.max_new, B, sp), "lmrl_gen_accept")
-            if k < self.max_new - 1:
-                self.ses.forward(self.next_tok, self.next_cnt, 1)
+        script, g = self._steer_rows(), self.traj
+        self._generate(self.ses, (self.ses,), temperature, top_k, top_p, sample_seed, 0.0, _lib.ptr(self.epoch), g["gen_active"], g["out_tok"], g["out_len"],
+                       self.next_tok, self.next_cnt, -1 if self.eos is None else int(self.eos), self.max_new, script, logits_out)
         ck(L.lmrl_tq_question(self._tq, tr, 1 if self.reuse_generated else 0, _lib.ptr(self.ses.len), _lib.ptr(self.oses.len), B, sp), "lmrl_tq_question")
         n_chunks = self._o_chunks[0 if first else 1]
         for j in range(n_chunks):
             ck(L.lmrl_tq_oracle_prompt(self._tq, tr, j, 16, n_chunks, _lib.ptr(self.chunk_tok), _lib.ptr(self.chunk_cnt), B, sp), "lmrl_tq_oracle_prompt")
             self.oses.forward(self.chunk_tok, self.chunk_cnt, 16, len_bound_after=self.pcap)
-        for k in range(self.omax_new):                  # the oracle: greedy, eos = the newline (GPT2EngineOracle: do_sample=False)
-            p = SampleParams(0.0, 0, 0, k, 0.0, 0.0, self.pad, None)
-            self.oses.sample(p, active=self.traj["o_active"], want_logprob=False)
-            ck(L.lmrl_gen_accept(_lib.ptr(self.oses.token), _lib.ptr(self.traj["o_active"]), _lib.ptr(self.traj["o_out_tok"]), _lib.ptr(self.traj["o_out_len"]),
-                                 _lib.ptr(self.o_next_tok), _lib.ptr(self.o_next_cnt), self._oeos, self.omax_new, B, sp), "lmrl_gen_accept")
-            if k < self.omax_new - 1:
-                self.oses.forward(self.o_next_tok, self.o_next_cnt, 1)
+        # the oracle: greedy, eos = the newline (GPT2EngineOracle: do_sample=False)
+        self._generate(self.oses, (self.oses,), 0.0, 0, 0.0, 0, 0.0, None, g["o_active"], g["o_out_tok"], g["o_out_len"], self.o_next_tok, self.o_next_cnt,
+                       self._oeos, self.omax_new)
         ans = self._answers
         ck(L.lmrl_tq_answer(self._tq, tr, _lib.ptr(ans), int(ans.shape[1]) if ans is not None else 0, B, sp), "lmrl_tq_answer")
         ck(L.lmrl_tq_judge(self._tq, tr, 1 if self.judge == "device" else 0, self.T, B, sp), "lmrl_tq_judge")
         self._feed_guesser(self._g_chunks)
-        self.epoch.add_(1)
-        if script is not None:
-            script[1].add_(1)
+        self._end_turn(script)
 
     def _reset(self, seeds, options, n_live: Optional[int]):
         """Hidden words (`random.Random(seed)._randbelow(n)` through lmrl_mt_*, or seed % n in deterministic mode), cleared records, and INITIAL_STR
@@ -344,50 +309,33 @@ class TwentyQuestionsRolloutEngine:
 
     def capture_turns(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, sample_seed: int = 0):
         """The two kinds of turn (an episode's first, and the later ones) as hipGraphs; `run_episode(..., use_graph=True)` replays them."""
-        import torch
-        t = torch
-        self._graph_args = (temperature, top_k, top_p, sample_seed)
-        self._logits = t.empty(self.B, self.eng.cfg.vocab_padded, dtype=t.float32, device=self.dev) if (top_k > 0 or top_p > 0.0) else None
+        self._begin_capture(temperature, top_k, top_p, sample_seed)
         self.turn_graphs = {}
         for first in (True, False) if self.T > 1 else (True,):
             self._reset([0] * self.B, None, None)
             if not first:               # a later turn keeps the oracle prompt's prefix of the turn before it: warm up and capture behind a first turn
                 self._turn(temperature, top_k, top_p, sample_seed, self._logits, True)
-            self._turn(temperature, top_k, top_p, sample_seed, self._logits, first)           # eager warm-up
-            t.cuda.synchronize()
-            g = t.cuda.CUDAGraph()
-            with t.cuda.graph(g, capture_error_mode="thread_local"):
-                self._turn(temperature, top_k, top_p, sample_seed, self._logits, first)
-            self.turn_graphs[first] = g
+            self.turn_graphs[first] = self._capture(temperature, top_k, top_p, sample_seed, self._logits, first)
         self._check_flags()
         return self.turn_graphs
+
+    def _graphs(self):
+        return self.turn_graphs
+
+    def _recapture(self, temperature, top_k, top_p, sample_seed):
+        self.capture_turns(temperature, top_k, top_p, sample_seed)
 
     def run_episode(self, seeds, options=None, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, sample_seed: int = 0, episode: int = 0,
                     use_graph: bool = False, sync_every: int = 8, max_turns: Optional[int] = None, n_live: Optional[int] = None):
         """One full episode for all B games; returns the device record dict (read after a sync; `records()` / `interactions()` / `ppo_records()`
         apply the host's re-judgement of flagged turns first).  `seeds`: one int per env; `options`: one dict or one per env, `{"deterministic":
         True}` as the env's reset.  The host peeks at the live flags every `sync_every` turns to stop early (0: never)."""
-        import torch
-        t = torch
-        if use_graph:
-            if not self.turn_graphs or self._graph_args != (temperature, top_k, top_p, sample_seed):
-                self.capture_turns(temperature, top_k, top_p, sample_seed)
-            logits = self._logits
-        else:
-            logits = t.empty(self.B, self.eng.cfg.vocab_padded, dtype=t.float32, device=self.dev) if (top_k > 0 or top_p > 0.0) else None
+        logits = self._episode_logits(use_graph, temperature, top_k, top_p, sample_seed)
         self._reset(seeds, options, n_live)
-        self.epoch.fill_(int(episode) << 12)
-        if self._script is not None:
-            self._script[1].zero_()
-        n = self.T if max_turns is None else min(self.T, max_turns)
-        for i in range(n):
-            if sync_every and i and i % sync_every == 0 and not bool(self.traj["live"].any().item()):
-                break
-            if use_graph:
-                self.turn_graphs[i == 0].replay()
-            else:
-                self._turn(temperature, top_k, top_p, sample_seed, logits, i == 0)
-        return self.traj
+        self._start_episode_counters(episode)
+        if use_graph:
+            return self._run_turns(lambda i: self.turn_graphs[i == 0].replay(), sync_every, max_turns)
+        return self._run_turns(lambda i: self._turn(temperature, top_k, top_p, sample_seed, logits, i == 0), sync_every, max_turns)
 
     # ---- host views --------------------------------------------------------------------------------------------------------------------
     def _check_flags(self):
@@ -443,18 +391,6 @@ class TwentyQuestionsRolloutEngine:
                             ep_reward=float(h["ep_reward"][b])))
         return out
 
-    def _decode(self, ids: List[int]) -> str:
-        if self.eos is not None and self.eos in ids:
-            ids = ids[: ids.index(self.eos) + 1]
-        try:
-            return self.tok.decode(ids, skip_special_tokens=True)
-        except TypeError:
-            special = getattr(self.tok, "all_special_ids", None)
-            if special is None:
-                special = [t for t in (getattr(self.tok, "pad_token_id", None),) if t is not None]
-            special = set(special)
-            return self.tok.decode([i for i in ids if i not in special])
-
     def interactions(self, n: Optional[int] = None):
         """The finished episodes (of the first `n` games) as `List[List[InteractionTransition]]` — what `interact_environment` returns for the same
         rollouts.  The question texts are decoded on the host from the recorded ids (`out_str_process(tokenizer.decode(ids))`)."""
@@ -465,7 +401,7 @@ class TwentyQuestionsRolloutEngine:
             hist = (Text(TQ.INITIAL_STR, False),)
             trans = []
             for i in range(len(rec["gen"])):
-                post_action = hist + (Text(maze_out_str_process(self._decode(rec["gen"][i])), True),)
+                post_action = hist + (Text(maze_out_str_process(decode_generation(self.tok, rec["gen"][i], self.eos)), True),)
                 post = post_action + (yes if rec["answer"][i] else no,)
                 trans.append(InteractionTransition(hist, post_action, post, float(rec["reward"][i]), bool(rec["done"][i])))
                 hist = post
@@ -474,31 +410,15 @@ class TwentyQuestionsRolloutEngine:
 
     @staticmethod
     def _summary(inter):
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
-        return dict(reward=summ(np.asarray([sum(t.reward for t in ep) for ep in inter], dtype=np.float32)),
-                    done=summ(np.asarray([ep[-1].done for ep in inter], dtype=np.float32)), length=summ([len(ep) for ep in inter]))
-
-    def _seeds(self, actual: int, seed_generator):
-        seeds = [0] * self.B
-        seeds[:actual] = [next(seed_generator) for _ in range(actual)] if seed_generator is not None else np.random.randint(0, 2 ** 31 - 1, size=actual).tolist()
-        return seeds
+        return dict(reward=summarize(np.asarray([sum(t.reward for t in ep) for ep in inter], dtype=np.float32)),
+                    done=summarize(np.asarray([ep[-1].done for ep in inter], dtype=np.float32)), length=summarize([len(ep) for ep in inter]))
 
     def text_env_eval(self, n_rollouts: int, seed_generator=None, env_options=None, temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0,
                       sample_seed: int = 0, interaction_callback=None, use_graph: bool = True, sync_every: int = 8):
         """`text_env_eval(env, policy, n_rollouts, bsize=B, env_options=...)` with the lock-step loop on the device: ceil(n / B) episode batches, the
         same (interactions, summary) return value.  The sampler's episode word keeps counting across calls."""
-        inter = []
-        launched = 0
-        while launched < n_rollouts:
-            actual = min(n_rollouts - launched, self.B)
-            self.run_episode(self._seeds(actual, seed_generator), env_options, temperature=temperature, top_k=top_k, top_p=top_p, sample_seed=sample_seed,
-                             episode=self.episodes, use_graph=use_graph, sync_every=sync_every, n_live=actual)
-            self.episodes += 1
-            launched += actual
-            for ep in self.interactions(actual):
-                inter.append(ep)
-                if interaction_callback is not None:
-                    interaction_callback(ep)
+        inter = self._eval_round(n_rollouts, seed_generator, env_options, interaction_callback,
+                                 dict(temperature=temperature, top_k=top_k, top_p=top_p, sample_seed=sample_seed, use_graph=use_graph, sync_every=sync_every))
         return inter, self._summary(inter)
 
     # ---- the online-RL hand-over -------------------------------------------------------------------------------------------------------
@@ -538,28 +458,12 @@ class TwentyQuestionsRolloutEngine:
         """One data-collection round of the PPO loop on the device: `text_env_eval(n_rollouts, bsize=B)` + `ppo_dataset_loader` ->
         (DevicePPODataset over all rollouts, all_kls, summary).  Per episode batch: the lock-step episode, then its PPO data while the record is in
         the engine's buffers; advantages whitened once over the action tokens of the whole round; `summary` has `text_env_eval`'s fields."""
-        import torch
-        from .algorithms.ppo_device import DevicePPODataset
-        from . import dist as D
-        parts, kls, stats = [], [], []
-        launched = 0
-        while launched < n_rollouts:
-            actual = min(n_rollouts - launched, self.B)
-            self.run_episode(self._seeds(actual, seed_generator), env_options, temperature=temperature, top_k=top_k, top_p=top_p, sample_seed=sample_seed,
-                             episode=self.episodes, use_graph=use_graph, n_live=actual)
-            self.episodes += 1
-            launched += actual
-            ds, kl = self.ppo_data(inference, gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, n=actual, use_advantage_whitening=False, **kw)
-            parts.append(ds); kls.append(kl)
-            nt = self.traj["n_turns"][:actual].cpu().numpy()
-            dn = self.traj["done"][:actual].cpu().numpy()
-            stats.append(np.stack([self.traj["ep_reward"][:actual].cpu().numpy().astype(np.float64), dn[np.arange(actual), np.maximum(nt - 1, 0)].astype(np.float64),
-                                   nt.astype(np.float64)]))
-        ds = DevicePPODataset.concat(parts)
-        if use_advantage_whitening:
-            adv = ds.old_advantages
-            ds.old_advantages = D.whiten_distributed(adv.view(-1), ds.should_take_action.view(-1), shift_mean=True).view(adv.shape)
-        st = np.concatenate(stats, axis=1)
-        summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
-        return ds, (kls[0] if len(kls) == 1 else torch.cat(kls)), dict(reward=summ(st[0].astype(np.float32)), done=summ(st[1].astype(np.float32)),
-                                                                       length=summ(st[2].astype(np.int64)))
+        return self._ppo_round(inference, n_rollouts, seed_generator, env_options, use_advantage_whitening,
+                               dict(temperature=temperature, top_k=top_k, top_p=top_p, sample_seed=sample_seed, use_graph=use_graph),
+                               dict(gamma=gamma, lam=lam, kl_weight=kl_weight, max_length=max_length, **kw))
+
+    def _round_stats(self, actual: int):
+        nt = self.traj["n_turns"][:actual].cpu().numpy()
+        dn = self.traj["done"][:actual].cpu().numpy()
+        return np.stack([self.traj["ep_reward"][:actual].cpu().numpy().astype(np.float64), dn[np.arange(actual), np.maximum(nt - 1, 0)].astype(np.float64),
+                         nt.astype(np.float64)])

@@ -366,6 +366,71 @@ def test_tq_ppo_records_and_device_ppo_data_equal_the_host_chain_path(matmul):
     ro.close()
 
 
+def test_ppo_rollouts_equals_the_round_done_by_hand():
+    """`ppo_rollouts` over two episode batches, the last one partial (B = 8, 11 rollouts: idle envs, the concat, ONE whitening over the round) ==
+    the same round done by hand on an identically built engine — per batch `run_episode(n_live=actual)` + `ppo_data(n=actual,
+    use_advantage_whitening=False)`, then `DevicePPODataset.concat` and one `dist.whiten_distributed` over the action tokens — bit for bit (both
+    sides run the same kernels on the same inputs); `summary` is mean / std / min / max of the records' `ep_reward`, last `done` and `n_turns`."""
+    import itertools
+    import torch
+    from lmrl_gym_amd import _lib, dist as D
+    from lmrl_gym_amd.algorithms.ppo_device import DevicePPODataset
+    from lmrl_gym_amd.algorithms.ppo_inference import GPT2PPOInference
+    from lmrl_gym_amd.tq_rollout import TwentyQuestionsRolloutEngine
+    from lmrl_gym_amd.train.gpt2_f32 import GPT2F32, LinearHeadF32
+    dev = _lib.require_gpu()
+    tok, eng, oeng, (cfg, sd) = _pair(dev, "bf16", seed=2)
+    B, T, G, N = 8, 4, 12, 11
+    plans = [_PLANS[b % len(_PLANS)] for b in range(B)]
+    questions = [[(plans[b][1] + [(None, 0)] * T)[t][0] for b in range(B)] for t in range(T)]
+    answers = np.array([[(plans[b][1] + [(None, -1)] * T)[t][1] for t in range(T)] for b in range(B)], dtype=np.int8)
+    ros = []
+    for _ in range(2):
+        ro = TwentyQuestionsRolloutEngine(eng, oeng, tok, _env(T), B, G, NL, MAX_IN, OMAX_IN)
+        ro.set_scripted_questions(questions, strength=60.0)
+        ro.set_scripted_answers(answers)
+        ros.append(ro)
+    gen = torch.Generator().manual_seed(6)
+    sd2 = {kk: v + 0.02 * torch.randn(v.shape, generator=gen) * v.abs().mean().clamp_min(1e-3) for kk, v in sd.items()}
+    pol, init = GPT2F32(sd2, cfg.n_head, device=dev, matmul="bf16"), GPT2F32(sd, cfg.n_head, device=dev, matmul="bf16")
+    vh = LinearHeadF32(dict(kernel=torch.randn(cfg.d_model, 1, generator=gen) * 0.05, bias=torch.tensor([0.2])), dev)
+    inf = GPT2PPOInference(pol, vh, tok.pad_token_id, initial_policy=init)
+    kw = dict(gamma=0.97, lam=0.9, kl_weight=0.05, max_length=ros[0].hist_bound + 1, bsize=64)
+    run = dict(temperature=1.0, sample_seed=8)
+    seed_gen = lambda: (plans[i % B][0] for i in itertools.count())     # env b plays plan b in every batch (deterministic mode: word = seed)
+    options = dict(deterministic=True)
+    ds, kls, summary = ros[0].ppo_rollouts(inf, N, seed_gen(), options, **kw, **run)
+    # ---- the same round by hand
+    ro, sg = ros[1], seed_gen()
+    parts, kl_parts, stats = [], [], []
+    for k, actual in enumerate((B, N - B)):
+        seeds = [0] * B
+        seeds[:actual] = [next(sg) for _ in range(actual)]
+        ro.run_episode(seeds, options, episode=k, use_graph=True, n_live=actual, **run)
+        d, kl = ro.ppo_data(inf, n=actual, use_advantage_whitening=False, **kw)
+        parts.append(d); kl_parts.append(kl)
+        rec = ro.records()[:actual]
+        stats += [(r["ep_reward"], float(r["done"][-1]), len(r["done"])) for r in rec]
+        assert int(ro.traj["n_turns"][actual:].sum().item()) == 0           # the idle envs of the partial batch recorded nothing
+    want = DevicePPODataset.concat(parts)
+    adv = want.old_advantages
+    want.old_advantages = D.whiten_distributed(adv.view(-1), want.should_take_action.view(-1), shift_mean=True).view(adv.shape)
+    assert len(ds) == len(want) == N
+    for name in DevicePPODataset.FIELDS:
+        assert torch.equal(getattr(ds, name), getattr(want, name)), name
+    assert ds.longest == want.longest and (ds.lengths is None) == (want.lengths is None)
+    assert ds.lengths is None or torch.equal(ds.lengths, want.lengths)
+    assert torch.equal(kls, torch.cat(kl_parts))
+    assert ros[0].episodes == 2 and bool(ds.should_take_action.any()) and float(ds.old_advantages.abs().max()) > 0
+    lens = [s[2] for s in stats]
+    assert min(lens) < T and max(lens) == T                                  # an episode was won early, another ran to the budget
+    summ = lambda x: dict(mean=np.mean(x), std=np.std(x), min=np.min(x), max=np.max(x))
+    st = np.asarray(stats, dtype=np.float64).T
+    assert summary == dict(reward=summ(st[0].astype(np.float32)), done=summ(st[1].astype(np.float32)), length=summ(st[2].astype(np.int64)))
+    for ro in ros:
+        ro.close()
+
+
 def test_engine_refuses_what_is_out_of_scope():
     from lmrl_gym_amd import _lib
     from lmrl_gym_amd.datasets import ByteTokenizer
